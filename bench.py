@@ -7,6 +7,10 @@ so the whole budget runs) through the C ABI.  value = collision-ch
 (reference semantics: every isInCollision call up to the first collision of an edge).  With N GPUs each rank
 plans its own queries against the scene rank 0 broadcast over RCCL (weak scaling, no per-iteration
 collectives).  rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (cpu_baseline null).  --full adds the CPU
+baselines after the timed region (the oracle on the same query, their parity with the GPU's step 0);
+--dump-outputs DIR writes the results of the last timed step.
 """
 import argparse
 import json
@@ -34,7 +38,14 @@ def parse():
     ap.add_argument("--warmup-samples", type=int, default=None,
                     help="budget of each warmup query (default: --samples, so warmup launches match timed ones)")
     ap.add_argument("--queries-per-gpu", type=int, default=1)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the CPU baselines "
+                         "(oracle on one thread and on all cores, its times to the first path, the many-query and "
+                         "large-tree variants) and their comparison with the GPU's step 0")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per query k: the path, the cost rows without "
+                         "their clock column and the result's counters and costs) as DIR/q<k>_<name>.npy, float64")
     ap.add_argument("--helpers", type=int, default=0,
                     help="helper workgroups per query (0 automatic, -1 none: e.g. for counter passes, which "
                          "serialise dispatches)")
@@ -244,6 +255,27 @@ def first_solution(orc, sc, pair, seed, max_iter=600):
     return r["t_first"] if r["t_first"] >= 0 else None
 
 
+# the fields of a result that the run's inputs determine (clock readings and the scouts' hit counts vary from run to
+# run); q<k>_stats.npy holds them in this order, the three-component costs flattened in place
+DUMP_STATS = ("status", "iterations", "first_solution_iter", "last_solution_iter", "configs_checked", "configs_valid",
+              "cost_best", "cost_theoretical", "nodes_start", "nodes_goal", "edges_start", "edges_goal",
+              "rewires_start", "rewires_goal", "connected_tree_is_start", "conn_node_b", "conn_node_a",
+              "nn_nodes_scanned", "near_nodes_scanned")
+
+
+def dump_outputs(out_dir, query_ids, results):
+    """--dump-outputs: the results plan_batch returned in the last timed step, one set of float64 arrays per query
+    (named by its query id in the job): path (waypoints x 8), cost_rows ([iteration, c_best, c_rev, c_prism] per
+    solution update; the clock column is left out) and stats (DUMP_STATS)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for qid, r in zip(query_ids, results):
+        stats = np.concatenate([np.atleast_1d(np.asarray(r[k], np.float64)) for k in DUMP_STATS])
+        arrays = {"path": r["path"], "cost_rows": r["cost_rows"][:, [0, 2, 3, 4]], "stats": stats}
+        for name, v in arrays.items():
+            np.save(os.path.join(out_dir, "q%d_%s.npy" % (qid, name)), np.ascontiguousarray(v, np.float64))
+
+
 def main():
     a = parse()
     import torch
@@ -315,7 +347,7 @@ def main():
         """The timed region: exactly a.steps planning steps of this rank's queries, bracketed by a barrier (several
         ranks; not for rank 0's run alone) and a device synchronisation on both sides."""
         totals = dict(checked=0, valid=0, iters=0, nn=0, near=0, plan_ms=0.0, launches=0)
-        first_t, first_host, steps0 = [], [], []
+        first_t, first_host, steps0, rs = [], [], [], []
         if world > 1 and sync_ranks:
             dist.barrier()
         torch.cuda.synchronize()
@@ -341,10 +373,12 @@ def main():
         torch.cuda.synchronize()
         if world > 1 and sync_ranks:
             dist.barrier()
-        return time.perf_counter() - t0, totals, steps0[0], first_t, first_host
+        return time.perf_counter() - t0, totals, steps0[0], first_t, first_host, rs
 
-    elapsed, totals, step0_all, first_t, first_host = timed_steps()
+    elapsed, totals, step0_all, first_t, first_host, last_step = timed_steps()
     step0 = step0_all[0]
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, mine, last_step)
 
     local_vec = [elapsed, totals["checked"], totals["valid"], totals["iters"], totals["nn"], totals["near"],
                  totals["plan_ms"], totals["launches"]]
@@ -437,9 +471,10 @@ def main():
             out["single_gpu_same_workload"]["how"] = (
                 "rank 0 planned its own per-GPU share (the same %d queries, seeds and budgets) again alone, the other "
                 "ranks waiting at a barrier" % len(mine))
-        if not a.no_cpu and world == 1 and a.workload == "c2" and a.iterations and a.iterations > a.cpu_iterations:
+        cpu = a.full and not a.no_cpu and world == 1
+        if cpu and a.workload == "c2" and a.iterations and a.iterations > a.cpu_iterations:
             out["cpu_baseline"] = cpu_window(a, gp, sc, pairs[0], a.seed, step0)
-        elif not a.no_cpu and world == 1:
+        elif cpu:
             cb = cpu_baseline(sc, pairs[0], a, step0_seed=a.seed, step_seeds=[a.seed + 1000 * step for step in
                                                                              range(a.steps)]
                               if a.queries_per_gpu == 1 else ())

@@ -7,16 +7,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REF_CONFIG = "/root/reference/squirrel_8dof_planner/config"
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (runs through the HIP C ABI)")
     config.addinivalue_line("markers", "slow: longer CPU-oracle runs")
-
-
-def have_reference():
-    return os.path.isdir(REF_CONFIG)
 
 
 @pytest.fixture(scope="session")

@@ -12,7 +12,7 @@ from oracle import octomap_bt, oracle as O
 from squirrel_motion_planner_amd import _lib as L
 from squirrel_motion_planner_amd import scenes
 from squirrel_motion_planner_amd.planner import Robot, Scene
-from conftest import REF_CONFIG, ROOT, have_reference
+from conftest import ROOT
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -86,10 +86,9 @@ def test_bt_decoder(room):
     a = Scene.from_bt(data).export()
     b = Scene.from_keys(keys, 0.05).export()
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-    if have_reference():  # the reference's own (pruned) file
-        raw = open(os.path.join(REF_CONFIG, room + ".bt"), "rb").read()
-        c = Scene.from_bt(raw).export()
-        assert np.array_equal(c[0], b[0]) and np.array_equal(c[1], b[1])
+    raw = open(os.path.join(GOLD, room + ".bt"), "rb").read()  # the reference's own (pruned) file
+    c = Scene.from_bt(raw).export()
+    assert np.array_equal(c[0], b[0]) and np.array_equal(c[1], b[1])
 
 
 def test_bt_parse_errors():

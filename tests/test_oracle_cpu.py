@@ -7,7 +7,6 @@ import pytest
 
 from oracle import octomap_bt, oracle as O
 from squirrel_motion_planner_amd import scenes
-from conftest import REF_CONFIG, have_reference
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -91,9 +90,8 @@ def test_room_fixture(room):
     f = np.load(os.path.join(GOLD, room + "_keys.npz"))
     assert float(f["res"]) == 0.05
     assert len(f["keys"]) in (5548, 4192, 4408)
-    if have_reference():
-        res, keys = octomap_bt.read_bt(open(os.path.join(REF_CONFIG, room + ".bt"), "rb").read())
-        assert np.array_equal(np.unique(keys, axis=0), np.unique(f["keys"].astype(np.int64), axis=0))
+    res, keys = octomap_bt.read_bt(open(os.path.join(GOLD, room + ".bt"), "rb").read())  # the reference's own file
+    assert np.array_equal(np.unique(keys, axis=0), np.unique(f["keys"].astype(np.int64), axis=0))
 
 
 def test_oracle_scene_box_gap_matches_bruteforce():

@@ -26,7 +26,7 @@ if [ -z "$SKIP_PMC" ]; then
   cp $R/profiles/${ROUND}_pmc_${TAG}.json ${P}_pmc.json
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 ${BENCH_LIMIT:-600} python bench.py "$@" > ${P}_bench.json 2> ${P}_bench.err
+  timeout -k 10 ${BENCH_LIMIT:-600} python bench.py --full "$@" > ${P}_bench.json 2> ${P}_bench.err
 fi
 if [ -z "$SKIP_KT" ]; then
   cd /tmp
