@@ -199,11 +199,9 @@ class BiRRTstarPlanner {
     smp_scene_opts_default(&o);
     o.resolution = resolution;
     o.insert_floor = 0;  // the node inserts its floor into the octree before setOctree (SP:889-902)
-    smp_scene* s = nullptr;
-    check(smp_scene_from_bt(data, size, &o, &s), "smp_scene_from_bt");
-    int st = smp_planner_set_scene(planner_, s);
-    smp_scene_destroy(s);
-    check(st, "smp_planner_set_scene");
+    // the scene is built on the GPU from the decoded keys (the same device arrays as smp_scene_from_bt +
+    // smp_planner_set_scene)
+    check(smp_planner_set_scene_bt(planner_, data, size, &o, nullptr), "smp_planner_set_scene_bt");
   }
 
   void setDisabledLinkMapCollisions(const std::vector<std::string>& links) {
@@ -242,14 +240,10 @@ class BiRRTstarPlanner {
     o.floor_center[0] = floor_x;
     o.floor_center[1] = floor_y;
     o.floor_distance = floor_distance;
-    smp_scene* s = nullptr;
-    check(smp_scene_from_octomap_msg(id.c_str(), resolution, binary ? 1 : 0,
-                                     reinterpret_cast<const uint8_t*>(data.empty() ? nullptr : data.data()),
-                                     data.size(), &o, &s),
-          "smp_scene_from_octomap_msg");
-    int st = smp_planner_set_scene(planner_, s);
-    smp_scene_destroy(s);
-    check(st, "smp_planner_set_scene");
+    check(smp_planner_set_scene_octomap_msg(planner_, id.c_str(), resolution, binary ? 1 : 0,
+                                            reinterpret_cast<const uint8_t*>(data.empty() ? nullptr : data.data()),
+                                            data.size(), &o, nullptr),
+          "smp_planner_set_scene_octomap_msg");
   }
 
   bool isConfigValid(const vector<double>& config, bool check_self_collision, bool check_map_collision) {
@@ -427,11 +421,7 @@ class MultiGpuPlanner {
     smp_scene_opts_default(&o);
     o.resolution = resolution;
     o.insert_floor = 0;
-    smp_scene* s = nullptr;
-    check(smp_scene_from_bt(data, size, &o, &s), "smp_scene_from_bt");
-    const int st = smp_planner_set_scene(planners_[0], s);
-    smp_scene_destroy(s);
-    check(st, "smp_planner_set_scene");
+    check(smp_planner_set_scene_bt(planners_[0], data, size, &o, nullptr), "smp_planner_set_scene_bt");
     check(smp_planners_share_scene(planners_.data(), (int)planners_.size(), 0), "smp_planners_share_scene");
   }
 

@@ -17,6 +17,10 @@
  *   smp_scene_from_grid        the same from a broadcast grid (multi-GPU: one RCCL broadcast per scene)
  *   smp_planner_create         BiRRTstarPlanner::initialize (birrt_star.cpp:11-326) on one GPU
  *   smp_planner_set_scene      BiRRTstarPlanner::setOctree (copies; caller keeps ownership)
+ *   smp_planner_set_scene_keys the node's map hand-off per request -- fetch the octomap, insert the floor, setOctree
+ *   smp_planner_set_scene_bt   (squirrel_8dof_planner.cpp:862-917, collision_checker.hpp:76-88) -- with the scene built
+ *   smp_planner_set_scene_ot   on the GPU: the keys (decoded on the host) are uploaded and every derived array is
+ *   smp_planner_set_scene_octomap_msg  computed by kernels, bit for bit what smp_scene_from_* + smp_planner_set_scene give
  *   smp_set_disabled_map_links BiRRTstarPlanner::setDisabledLinkMapCollisions (birrt_star.cpp:6916-6919)
  *   smp_plan                   reset_planner_and_config + setPlanningSceneInfo + init_planner + run_planner
  *                              + getJointTrajectoryRef (squirrel_8dof_planner.cpp:1221-1248,
@@ -194,6 +198,29 @@ int smp_scene_export(const smp_scene* s, uint64_t* bits, uint16_t* d2);
 int smp_planner_create(int device, const smp_robot* robot, const smp_params* params, smp_planner** out);
 void smp_planner_destroy(smp_planner* p);
 int smp_planner_set_scene(smp_planner* p, const smp_scene* s);
+/* The same scene as smp_scene_from_keys / _bt / _ot / _octomap_msg followed by smp_planner_set_scene, built on the
+ * planner's GPU (dilation, exact squared distance transform, bricks, byte field, slab fields as kernels on the
+ * planner's stream); the resulting device arrays are identical.  Arguments, floor insertion and status codes are
+ * those of the smp_scene_from_* call of the same name; on an argument or parse error the planner keeps its previous
+ * scene.  Grids with a line of more than 32768 cells along y or z are left to the host path (SMP_ERR_ARG). */
+typedef struct smp_scene_build {   /* may be NULL */
+  int dims[3];
+  double origin[3];
+  double resolution;
+  int64_t n_occupied;      /* distinct occupied cells, as smp_scene_info reports */
+  double bbox_min[3], bbox_max[3];
+  double kernel_ms;        /* HIP events around the build kernels on the planner's stream */
+  double total_ms;         /* host clock, call entry to return (upload and final sync included) */
+} smp_scene_build;
+int smp_planner_set_scene_keys(smp_planner* p, const uint16_t* keys_xyz, int64_t n, const smp_scene_opts* opts,
+                               smp_scene_build* info);
+int smp_planner_set_scene_bt(smp_planner* p, const uint8_t* data, size_t size, const smp_scene_opts* opts,
+                             smp_scene_build* info);
+int smp_planner_set_scene_ot(smp_planner* p, const uint8_t* data, size_t size, const smp_scene_opts* opts,
+                             smp_scene_build* info);
+int smp_planner_set_scene_octomap_msg(smp_planner* p, const char* id, double resolution, int binary,
+                                      const uint8_t* data, size_t size, const smp_scene_opts* opts,
+                                      smp_scene_build* info);
 /* Planner parameters for subsequent smp_plan calls (activate/deactivateTreeOptimization,
  * activate/deactivateInformedSampling, birrt_star.h:57-63; setEdgeCostWeights keeps weights 1). */
 int smp_planner_set_params(smp_planner* p, const smp_params* params);

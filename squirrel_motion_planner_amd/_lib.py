@@ -87,6 +87,12 @@ class SceneDevice(ctypes.Structure):
                 ("n_prim", _i), ("has_d2b", _i), ("bricks", _p), ("d2", _p), ("d2b", _p), ("slab", _p)]
 
 
+class SceneBuild(ctypes.Structure):
+    """smp_scene_build: geometry, occupied cells and timing of a device scene build."""
+    _fields_ = [("dims", _i * 3), ("origin", _d * 3), ("resolution", _d), ("n_occupied", _i64), ("bbox_min", _d * 3),
+                ("bbox_max", _d * 3), ("kernel_ms", _d), ("total_ms", _d)]
+
+
 # (name, restype, argtypes) of every symbol declared in include/smp_gpu.h
 EXPORTS = [
     ("smp_params_default", None, [ctypes.POINTER(Params)]),
@@ -108,6 +114,11 @@ EXPORTS = [
     ("smp_planner_create", _i, [_i, _p, ctypes.POINTER(Params), ctypes.POINTER(_p)]),
     ("smp_planner_destroy", None, [_p]),
     ("smp_planner_set_scene", _i, [_p, _p]),
+    ("smp_planner_set_scene_keys", _i, [_p, _p, _i64, ctypes.POINTER(SceneOpts), ctypes.POINTER(SceneBuild)]),
+    ("smp_planner_set_scene_bt", _i, [_p, _p, ctypes.c_size_t, ctypes.POINTER(SceneOpts), ctypes.POINTER(SceneBuild)]),
+    ("smp_planner_set_scene_ot", _i, [_p, _p, ctypes.c_size_t, ctypes.POINTER(SceneOpts), ctypes.POINTER(SceneBuild)]),
+    ("smp_planner_set_scene_octomap_msg", _i, [_p, ctypes.c_char_p, _d, _i, _p, ctypes.c_size_t,
+                                               ctypes.POINTER(SceneOpts), ctypes.POINTER(SceneBuild)]),
     ("smp_planner_set_params", _i, [_p, ctypes.POINTER(Params)]),
     ("smp_planner_get_params", _i, [_p, ctypes.POINTER(Params)]),
     ("smp_set_disabled_map_links", _i, [_p, ctypes.POINTER(ctypes.c_char_p), _i]),

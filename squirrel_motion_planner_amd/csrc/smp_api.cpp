@@ -20,6 +20,7 @@
 #include "smp_ik.h"
 #include "smp_math.h"
 #include "smp_plan.h"
+#include "smp_scene.h"
 #include "smp_types.h"
 
 namespace smp {
@@ -123,6 +124,11 @@ struct smp_planner {
   DBuf<uint16_t> d_d2;
   DBuf<uint8_t> d_d2b;
   DBuf<uint16_t> d_slab;           // per-primitive 2-D slab fields (SceneDev::slab), n_prim x nx x ny
+  // scratch of the device scene build (smp_planner_set_scene_keys): uploaded keys, two bit grids, the occupied-cell
+  // count, the slabs' layer ranges
+  DBuf<uint16_t> d_keys;
+  DBuf<unsigned long long> d_sbits, d_sdil, d_scount;
+  DBuf<int> d_sk01;
   SceneDev sc{};
   bool have_scene = false;
   double scene_res = 0.05;
@@ -413,6 +419,7 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
       if (hipFuncGetAttributes(&fa, k) == hipSuccess) need = std::max(need, (size_t)fa.localSizeBytes);
     need = std::max(need, check_kernels_private_bytes());
     need = std::max(need, ik_kernels_private_bytes());
+    need = std::max(need, scene_kernels_private_bytes());
     size_t cur = 0;
     if (hipDeviceGetLimit(&cur, hipLimitStackSize) == hipSuccess && cur < need) {
       need = (need + 255) / 256 * 256;
@@ -460,6 +467,7 @@ void smp_planner_destroy(smp_planner* p) {
   p->d_qdev.release(); p->d_counts.release(); p->d_lfin.release(); p->d_cq.release(); p->d_valid.release();
   p->d_ik_tasks.release(); p->d_ik_out.release(); p->d_ik_best.release(); p->d_path_edges.release();
   p->d_bricks.release(); p->d_d2.release(); p->d_d2b.release(); p->d_slab.release();
+  p->d_keys.release(); p->d_sbits.release(); p->d_sdil.release(); p->d_scount.release(); p->d_sk01.release();
   if (p->d_rb) (void)hipFree(p->d_rb);
   if (p->d_mc) (void)hipFree(p->d_mc);
   if (p->ev0) (void)hipEventDestroy(p->ev0);
@@ -549,6 +557,164 @@ int smp_planner_set_scene(smp_planner* p, const smp_scene* s) {
   p->have_scene = true;
   p->scene_res = s->h.res;
   return update_mapcfg(p);
+}
+
+// The planner's scene built on the device from occupied keys (DESIGN.md "Scene build", smp_scene.hip): the arrays
+// scene_from_keys + smp_planner_set_scene derive on the host, bit for bit.  The grid geometry is scene_from_keys' own
+// arithmetic on the key list (O(n), and it carries the double rounding of the origin); everything per cell runs in
+// kernels on the planner's stream.
+static int set_scene_keys_device(smp_planner* p, const uint16_t* keys, int64_t n, double res, double z_offset,
+                                 smp_scene_build* info, std::chrono::steady_clock::time_point t0) {
+  if (int b_ = busy_check(p)) return b_;
+  const RobotDev& d = p->robot.dev;
+  for (int k = 0; k < d.n_prim; ++k)
+    if (d.prim_rxy[k] > GRID_REACH) {  // the padding would not keep a primitive outside the grid free
+      fprintf(stderr, "smp_gpu: primitive reach %.3f m exceeds the grid padding\n", d.prim_rxy[k]);
+      return SMP_ERR_ARG;
+    }
+  int nx = 1, ny = 1, nz = 1, kmin[3] = {0, 0, 0};
+  double org[3] = {0.0, 0.0, 0.0 + z_offset}, bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
+  if (n > 0) {
+    int kmax[3] = {-1, -1, -1};
+    kmin[0] = kmin[1] = kmin[2] = 1 << 30;
+    for (int64_t i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) {
+        const int k = keys[i * 3 + a];
+        kmin[a] = std::min(kmin[a], k);
+        kmax[a] = std::max(kmax[a], k);
+      }
+    const int pad = grid_pad_cells(res);
+    for (int a = 0; a < 3; ++a) {
+      bmin[a] = (double)(kmin[a] - KEY_OFFSET) * res;
+      bmax[a] = (double)(kmax[a] - KEY_OFFSET + 1) * res;
+      kmin[a] -= pad;
+      kmax[a] += pad;
+    }
+    nx = kmax[0] - kmin[0] + 1;
+    ny = kmax[1] - kmin[1] + 1;
+    nz = kmax[2] - kmin[2] + 1;
+    org[0] = (double)(kmin[0] - KEY_OFFSET) * res;
+    org[1] = (double)(kmin[1] - KEY_OFFSET) * res;
+    org[2] = (double)(kmin[2] - KEY_OFFSET) * res + z_offset;
+  } else {
+    n = 0;
+  }
+  if (!scene_build_fits(nx, ny, nz, d.n_prim)) {
+    fprintf(stderr, "smp_gpu: a %d x %d x %d grid is beyond the device scene build (use smp_planner_set_scene)\n", nx, ny, nz);
+    return SMP_ERR_ARG;
+  }
+  const int bnx = (nx + 3) / 4, bny = (ny + 3) / 4, bnz = (nz + 3) / 4;
+  const size_t nc = (size_t)nx * ny * nz, plane = (size_t)nx * ny, words = scene_words(nx, ny, nz, d.n_prim);
+  uint32_t tmax = 0;  // byte copy of the field when every sphere's threshold is below 255 (SceneDev.d2b)
+  for (int k = 0; k < d.n_sph; ++k) tmax = std::max(tmax, sphere_threshold(d.sph_r[k], res));
+  const bool bytes = tmax < 255;
+  int k01[2 * MAX_PRIM] = {0};
+  {
+    int k0[MAX_PRIM], k1[MAX_PRIM];
+    prim_slab_layers(d, org[2], res, nz, k0, k1);
+    for (int k = 0; k < d.n_prim; ++k) { k01[2 * k] = k0[k]; k01[2 * k + 1] = k1[k]; }
+  }
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(p->d_keys.reserve((size_t)n * 3));
+  HIPCHK(p->d_sbits.reserve(words));
+  HIPCHK(p->d_sdil.reserve(words));
+  HIPCHK(p->d_scount.reserve(1));
+  HIPCHK(p->d_sk01.reserve(2 * MAX_PRIM));
+  HIPCHK(p->d_bricks.reserve((size_t)bnx * bny * bnz));
+  HIPCHK(p->d_d2.reserve(nc));
+  if (bytes) HIPCHK(p->d_d2b.reserve(nc));
+  if (d.n_prim > 0) HIPCHK(p->d_slab.reserve(plane * d.n_prim));
+  if (n > 0) HIPCHK(hipMemcpyAsync(p->d_keys.p, keys, (size_t)n * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemcpyAsync(p->d_sk01.p, k01, sizeof(k01), hipMemcpyHostToDevice, p->stream));
+  SceneBuildArgs a{};
+  a.keys = p->d_keys.p; a.n_keys = n;
+  for (int c = 0; c < 3; ++c) a.kmin[c] = kmin[c];
+  a.nx = nx; a.ny = ny; a.nz = nz;
+  a.bits = p->d_sbits.p; a.dil = p->d_sdil.p; a.count = p->d_scount.p;
+  a.bricks = reinterpret_cast<unsigned long long*>(p->d_bricks.p);
+  a.d2 = p->d_d2.p;
+  a.d2b = bytes ? p->d_d2b.p : nullptr;
+  a.n_prim = d.n_prim; a.k01 = p->d_sk01.p; a.slab = p->d_slab.p;
+  HIPCHK(hipEventRecord(p->ev0, p->stream));
+  HIPCHK(launch_scene_build(p->stream, a));
+  HIPCHK(hipEventRecord(p->ev1, p->stream));
+  unsigned long long n_occ = 0;
+  HIPCHK(hipMemcpyAsync(&n_occ, p->d_scount.p, sizeof(n_occ), hipMemcpyDeviceToHost, p->stream));
+  p->sc.nx = nx; p->sc.ny = ny; p->sc.nz = nz;
+  p->sc.bnx = bnx; p->sc.bny = bny;
+  p->sc.ox = org[0]; p->sc.oy = org[1]; p->sc.oz = org[2]; p->sc.res = res; p->sc.inv_res = 1.0 / res;
+  p->sc.bricks = p->d_bricks.p;
+  p->sc.d2 = p->d_d2.p;
+  p->sc.d2b = bytes ? p->d_d2b.p : nullptr;
+  for (int k = 0; k < MAX_PRIM; ++k) p->sc.slab[k] = k < d.n_prim ? p->d_slab.p + k * plane : nullptr;
+  p->have_scene = true;
+  p->scene_res = res;
+  // The one synchronisation of this path: update_mapcfg waits for the stream after its own small upload, which
+  // covers the kernels (kernel_ms, the occupied-cell count) and the key upload (the caller's buffer, k01).
+  if (int st = update_mapcfg(p)) return st;
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+  if (info) {
+    info->dims[0] = nx; info->dims[1] = ny; info->dims[2] = nz;
+    for (int c = 0; c < 3; ++c) { info->origin[c] = org[c]; info->bbox_min[c] = bmin[c]; info->bbox_max[c] = bmax[c]; }
+    info->resolution = res;
+    info->n_occupied = (int64_t)n_occ;
+    info->kernel_ms = ms;
+    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  return SMP_OK;
+}
+
+int smp_planner_set_scene_keys(smp_planner* p, const uint16_t* keys, int64_t n, const smp_scene_opts* o,
+                               smp_scene_build* info) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!p || !o || (n > 0 && !keys) || !(o->resolution > 0)) return SMP_ERR_ARG;
+  if (!o->insert_floor) return set_scene_keys_device(p, keys, n, o->resolution, o->z_offset, info, t0);
+  std::vector<uint16_t> k(keys, keys + 3 * std::max<int64_t>(n, 0));
+  floor_keys(o->floor_center[0], o->floor_center[1], o->resolution, o->floor_distance, &k);
+  return set_scene_keys_device(p, k.data(), (int64_t)k.size() / 3, o->resolution, o->z_offset, info, t0);
+}
+
+// Occupied keys + free leaves of an octomap stream (the host decoders: the octree walk is sequential and small, and
+// the floor rule depends on the free leaves), then the keys path.
+static int set_scene_octomap_device(smp_planner* p, bool full, bool header, const uint8_t* data, size_t size,
+                                    double res, const smp_scene_opts* o, smp_scene_build* info,
+                                    std::chrono::steady_clock::time_point t0) {
+  std::vector<uint16_t> k;
+  std::vector<FreeLeaf> fl;
+  try {
+    if (full) octomap_ot_keys(data, size, &res, &k, &fl, header);
+    else octomap_bt_keys(data, size, &res, &k, &fl, header);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "smp_gpu: %s\n", e.what());
+    return SMP_ERR_PARSE;
+  }
+  if (!(res > 0)) return SMP_ERR_ARG;
+  if (o->insert_floor) floor_keys(o->floor_center[0], o->floor_center[1], res, o->floor_distance, &k, &fl);
+  return set_scene_keys_device(p, k.data(), (int64_t)k.size() / 3, res, o->z_offset, info, t0);
+}
+
+int smp_planner_set_scene_bt(smp_planner* p, const uint8_t* data, size_t size, const smp_scene_opts* o,
+                             smp_scene_build* info) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!p || !data || !o) return SMP_ERR_ARG;
+  return set_scene_octomap_device(p, false, true, data, size, 0.0, o, info, t0);
+}
+
+int smp_planner_set_scene_ot(smp_planner* p, const uint8_t* data, size_t size, const smp_scene_opts* o,
+                             smp_scene_build* info) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!p || !data || !o) return SMP_ERR_ARG;
+  return set_scene_octomap_device(p, true, true, data, size, 0.0, o, info, t0);
+}
+
+int smp_planner_set_scene_octomap_msg(smp_planner* p, const char* id, double resolution, int binary,
+                                      const uint8_t* data, size_t size, const smp_scene_opts* o,
+                                      smp_scene_build* info) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!p || !id || !o || (size > 0 && !data) || !(resolution > 0)) return SMP_ERR_ARG;
+  if (std::strcmp(id, "OcTree") != 0) return SMP_ERR_PARSE;  // as smp_scene_from_octomap_msg
+  return set_scene_octomap_device(p, binary == 0, false, data, size, resolution, o, info, t0);
 }
 
 // Device-resident scene of a planner (multi-GPU): the arrays smp_planner_set_scene derived for

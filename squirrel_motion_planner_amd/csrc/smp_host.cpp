@@ -226,6 +226,22 @@ void prim_slabs(const RobotDev& d, const SceneHost& s, std::vector<std::vector<u
   }
 }
 
+// The layer range [k0, k1] prim_slabs projects for every primitive (k0 > k1: none), from the grid's z origin,
+// resolution and layer count alone: the device scene build (smp_scene.hip) projects the same layers.
+void prim_slab_layers(const RobotDev& d, double oz, double res, int nz, int* k0s, int* k1s) {
+  double zc[MAX_PRIM];
+  prim_z(d, zc);
+  for (int p = 0; p < d.n_prim; ++p) {
+    const double hz = d.prim_type[p] == 1 ? d.prim_h[p * 3 + 2] : d.prim_h[p * 3 + 1];
+    const double zlo = zc[p] - hz - 1e-6, zhi = zc[p] + hz + 1e-6;
+    int k0 = std::max(0, (int)std::floor((zlo - oz) / res) - 1), k1 = std::min(nz - 1, (int)std::floor((zhi - oz) / res) + 1);
+    while (k0 <= k1 && oz + (double)(k0 + 1) * res < zlo) ++k0;
+    while (k1 >= k0 && oz + (double)k1 * res > zhi) --k1;
+    k0s[p] = k0;
+    k1s[p] = k1;
+  }
+}
+
 // d2 is a lower bound of (distance from any point of the cell to any occupied box / res)^2, so a sphere of
 // radius r whose centre cell has d2 > T cannot touch an occupied box; the 1e-6 m margin absorbs rounding.
 uint32_t sphere_threshold(double r, double res) {

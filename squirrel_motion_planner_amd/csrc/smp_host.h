@@ -68,6 +68,8 @@ uint32_t sphere_threshold(double r, double res);
 // Per-primitive 2-D box-gap fields of a scene (SceneDev::slab): occupancy projected over the layers the primitive's
 // constant z range touches, dilated 3x3, squared EDT (cells).
 void prim_slabs(const RobotDev& d, const SceneHost& s, std::vector<std::vector<uint16_t>>* out);
+// The layers [k0[p], k1[p]] prim_slabs projects for primitive p (k0 > k1: none) in a grid of nz layers from oz.
+void prim_slab_layers(const RobotDev& d, double oz, double res, int nz, int* k0, int* k1);
 // Flat self-collision pair lists (sphere pairs, primitive-sphere pairs) from pair_a / pair_b.
 void finish_pairs(RobotDev* d);
 

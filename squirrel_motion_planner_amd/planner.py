@@ -184,6 +184,64 @@ class GpuPlanner:
         check(lib().smp_planner_set_scene(self.h, scene.h), "smp_planner_set_scene")
         self.scene = scene
 
+    # The scene built on the GPU (smp_planner_set_scene_*): the same device arrays as Scene.from_* + set_scene, derived
+    # by kernels from the occupied keys.  Each returns the smp_scene_build fields as a dict.
+    def _built(self, status, info, what):
+        check(status, what)
+        self.scene = None
+        d = {f: getattr(info, f) for f, _ in L.SceneBuild._fields_}
+        for f in ("dims", "origin", "bbox_min", "bbox_max"):
+            d[f] = tuple(d[f])
+        return d
+
+    def set_scene_keys(self, keys, res, z_offset=-0.02, floor_center=None, floor_distance=3.0):
+        keys = np.ascontiguousarray(np.asarray(keys).reshape(-1, 3), np.uint16)
+        o = Scene._opts(z_offset, floor_center, floor_distance)
+        o.resolution = res
+        info = L.SceneBuild()
+        return self._built(lib().smp_planner_set_scene_keys(self.h, keys.ctypes.data_as(ctypes.c_void_p), len(keys),
+                                                            ctypes.byref(o), ctypes.byref(info)),
+                           info, "smp_planner_set_scene_keys")
+
+    def set_scene_bt(self, data, z_offset=-0.02, floor_center=None, floor_distance=3.0):
+        """Octomap binary file (.bt) bytes."""
+        buf = ctypes.create_string_buffer(bytes(data), len(data))
+        o = Scene._opts(z_offset, floor_center, floor_distance)
+        info = L.SceneBuild()
+        return self._built(lib().smp_planner_set_scene_bt(self.h, buf, len(data), ctypes.byref(o), ctypes.byref(info)),
+                           info, "smp_planner_set_scene_bt")
+
+    def set_scene_ot(self, data, z_offset=-0.02, floor_center=None, floor_distance=3.0):
+        """Octomap full-format file (.ot) bytes."""
+        buf = ctypes.create_string_buffer(bytes(data), len(data))
+        o = Scene._opts(z_offset, floor_center, floor_distance)
+        info = L.SceneBuild()
+        return self._built(lib().smp_planner_set_scene_ot(self.h, buf, len(data), ctypes.byref(o), ctypes.byref(info)),
+                           info, "smp_planner_set_scene_ot")
+
+    def set_scene_octomap_msg(self, id, resolution, binary, data, z_offset=-0.02, floor_center=None,
+                              floor_distance=3.0):
+        """octomap_msgs/Octomap fields (squirrel_8dof_planner.cpp:875-883)."""
+        data = bytes(data)
+        buf = ctypes.create_string_buffer(data, max(len(data), 1))
+        o = Scene._opts(z_offset, floor_center, floor_distance)
+        info = L.SceneBuild()
+        return self._built(lib().smp_planner_set_scene_octomap_msg(
+            self.h, id.encode() if isinstance(id, str) else id, float(resolution), int(bool(binary)), buf, len(data),
+            ctypes.byref(o), ctypes.byref(info)), info, "smp_planner_set_scene_octomap_msg")
+
+    def scene_arrays(self):
+        """The planner's device-resident scene copied to the host: (layout, bricks, d2, d2b or None, slab) as numpy
+        arrays (smp_planner_scene_device with host buffers as destinations)."""
+        v = self.scene_device()
+        bricks = np.zeros(v.n_bricks, np.uint64)
+        d2 = np.zeros(v.n_cells, np.uint16)
+        d2b = np.zeros(v.n_cells, np.uint8) if v.has_d2b else None
+        slab = np.zeros(v.n_prim * v.dims[0] * v.dims[1], np.uint16)
+        v = self.scene_device(bricks.ctypes.data, d2.ctypes.data, d2b.ctypes.data if v.has_d2b else 0,
+                              slab.ctypes.data if slab.size else 0)
+        return v, bricks, d2, d2b, slab
+
     def scene_device(self, bricks=0, d2=0, d2b=0, slab=0):
         """smp_planner_scene_device: geometry and sizes of the planner's device-resident scene; each non-zero device
         address (e.g. a torch tensor's data_ptr() on any GPU) receives a device-to-device copy of that array."""
