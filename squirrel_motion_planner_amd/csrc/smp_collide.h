@@ -211,6 +211,13 @@ __device__ __forceinline__ double quad_bcast(double v) {
   return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
 
+// Value of lane I of this lane's row of 16 lanes (one 64-bit DPP row broadcast).  Lane I of the row must be active.
+template <int I>
+__device__ __forceinline__ double row_bcast(double v) {
+  static_assert(I >= 0 && I < 16, "lane of the row");
+  return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + I, 0xF, 0xF, true);
+}
+
 // Cooperative exact map test of sphere centre cc, radius r by one wavefront.  The brick words covering the
 // reach (<= 64) are loaded once, one per lane, and handed to the lanes testing their cells by shuffles; then
 // lanes sweep the cells in reach (exact box test, ballot early exit).  Larger reaches load per cell.
@@ -929,7 +936,7 @@ struct WideWave {
     } c;
   } u;
   struct {
-    double fr[MAX_BODY][12];                // B -> centres: body frames (R row-major, p)
+    double fr[MAX_BODY + 1][12];            // B -> centres: body frames (R row-major, p); row MAX_BODY: no body
   } v;
   uint32_t cand[(MAX_SPH + 31) / 32];       // this wavefront's candidate spheres (map sweep)
   uint32_t pcand;                           // this wavefront's candidate primitives
@@ -943,6 +950,114 @@ struct WideLds {
   int coll[NWAVE];                          // configuration c: 1 = in collision
 };
 
+// What a lane of collide_wide needs of the robot model, the map configuration and the scene, and what never changes
+// during a launch: read once per workgroup (wide_const) and kept in registers over all the tiles it runs.  A lane always
+// serves the same chain step (stage A: step `lane`), the same items of the centres stage (item u * 64 + lane: a sphere,
+// then the primitives) whatever the tile, so its indices into the model are constants; the tile then reads the model's
+// fp64 values at known addresses in one batch per stage instead of index -> value chains of LDS round trips.  The scene
+// scalars are wave-uniform (uniform_scene): a caller's SceneDev may live in private memory.
+struct WideConst {
+  SceneDev sc;                  // scalars and field pointers in scalar registers (slab[] is not copied: `slab` below)
+  int nch, nit, has_map;        // chain steps; items (spheres + primitives); a scene is present
+  unsigned long long bodies;    // chain step k: its body + 1 in bits 4k .. 4k + 3, 0 = none (MAX_BODY <= 15)
+  int a_ty, a_j;                // stage A, lane k < nch: type of chain step k and its joint (0 for a fixed step)
+  // centres, item u * 64 + lane: 0 none, 1 sphere, 2 primitive, | 4 if it is tested against the map; its body; the
+  // offsets (in doubles from the RobotDev) of its centre and, for a primitive, of its x axis; its prefilter threshold
+  int kind[2], body[2], cb[2];
+  uint32_t T[2];
+  int ab;                       // (a lane holds at most one primitive: MAX_PRIM < 64)
+  int prim;                     // that primitive's index, else 0
+  const uint16_t* slab;         // and its slab field
+};
+static_assert(MAX_BODY <= 15 && MAX_CHAIN <= 16, "body + 1 of every chain step in 4 bits of a 64-bit word");
+static_assert(MAX_SPH + MAX_PRIM <= 128 && MAX_PRIM < 64, "two items per lane, at most one of them a primitive");
+static_assert(offsetof(RobotDev, sph_cb) % 8 == 0 && offsetof(RobotDev, prim_cb) % 8 == 0 &&
+              offsetof(RobotDev, prim_ab) % 8 == 0, "model offsets in doubles");
+
+// Fills a wavefront's WideConst from the staged model (rb, mc: LDS) and the caller's scene.  All lanes.
+__device__ __forceinline__ WideConst wide_const(const RobotDev* __restrict__ rb, const SceneDev& sc_in,
+                                                const MapCfg* __restrict__ mc) {
+  WideConst K;
+  K.sc = uniform_scene(sc_in);
+  const int lane = threadIdx.x & 63;
+  const int nsph = __builtin_amdgcn_readfirstlane(rb->n_sph), npr = __builtin_amdgcn_readfirstlane(rb->n_prim);
+  K.nch = __builtin_amdgcn_readfirstlane(rb->n_chain);
+  K.nit = nsph + npr;
+  K.has_map = __builtin_amdgcn_readfirstlane(mc->has_map);
+  unsigned long long bodies = 0;
+  for (int k = 0; k < K.nch; ++k)
+    bodies |= (unsigned long long)(unsigned)(__builtin_amdgcn_readfirstlane(rb->ch_body[k]) + 1) << (4 * k);
+  K.bodies = bodies;
+  const int ka = lane < K.nch ? lane : 0;
+  K.a_ty = lane < K.nch ? rb->ch_type[ka] : 0;
+  K.a_j = K.a_ty != 0 ? rb->ch_joint[ka] : 0;
+  K.ab = 0;
+  K.prim = 0;
+  K.slab = nullptr;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int it = u * 64 + lane;
+    K.kind[u] = 0; K.body[u] = 0; K.cb[u] = (int)(offsetof(RobotDev, sph_cb) / 8); K.T[u] = 0;
+    if (it < nsph) {
+      K.kind[u] = 1 | (mc->map_on[it] ? 4 : 0);
+      K.body[u] = rb->sph_body[it];
+      K.cb[u] = (int)(offsetof(RobotDev, sph_cb) / 8) + it * 3;
+      K.T[u] = mc->T[it];
+    } else if (it < nsph + npr) {
+      const int p = it - nsph;
+      K.kind[u] = 2 | (mc->p_map_on[p] ? 4 : 0);
+      K.body[u] = rb->prim_body[p];
+      K.cb[u] = (int)(offsetof(RobotDev, prim_cb) / 8) + p * 3;
+      K.T[u] = mc->pT[p];
+      K.ab = (int)(offsetof(RobotDev, prim_ab) / 8) + p * 3;
+      K.prim = p;
+      K.slab = sc_in.slab[p];
+    }
+  }
+  if (K.ab == 0) K.ab = K.cb[0];  // (a readable address for the lanes without a primitive)
+  return K;
+}
+
+// LDS copy of a workgroup's WideConst, for a caller that cannot keep it in registers between its tiles (a publisher's
+// own and stolen tiles, a call each): the per-lane part is the same in every wavefront, one row per lane; the scene
+// scalars are taken from the caller's scene again (uniform_scene), as they are not per lane.
+struct WideStash {
+  struct Lane {
+    int a_ty, a_j, kind[2], body[2], cb[2];
+    uint32_t T[2];
+    int ab, prim;
+    const uint16_t* slab;
+  } lane[64];
+  unsigned long long bodies;
+  int nch, nit, has_map;
+};
+// Stores K (any wavefront's) into S.  Threads 0..63; the caller's barrier publishes it.
+__device__ __forceinline__ void wide_const_store(WideStash& S, const WideConst& K) {
+  if (threadIdx.x < 64) {
+    WideStash::Lane& l = S.lane[threadIdx.x];
+    l.a_ty = K.a_ty; l.a_j = K.a_j;
+    for (int u = 0; u < 2; ++u) { l.kind[u] = K.kind[u]; l.body[u] = K.body[u]; l.cb[u] = K.cb[u]; l.T[u] = K.T[u]; }
+    l.ab = K.ab; l.prim = K.prim; l.slab = K.slab;
+  }
+  if (threadIdx.x == 0) { S.bodies = K.bodies; S.nch = K.nch; S.nit = K.nit; S.has_map = K.has_map; }
+}
+// The WideConst of this wavefront from S: one batch of LDS reads at addresses known from the lane number.
+__device__ __forceinline__ WideConst wide_const_load(const WideStash& S, const SceneDev& sc_in) {
+  WideConst K;
+  K.sc = uniform_scene(sc_in);
+  const WideStash::Lane& l = S.lane[threadIdx.x & 63];
+  K.a_ty = l.a_ty; K.a_j = l.a_j;
+  for (int u = 0; u < 2; ++u) { K.kind[u] = l.kind[u]; K.body[u] = l.body[u]; K.cb[u] = l.cb[u]; K.T[u] = l.T[u]; }
+  K.ab = l.ab; K.prim = l.prim; K.slab = l.slab;
+  const unsigned long long b = S.bodies;
+  K.bodies = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+             (unsigned)__builtin_amdgcn_readfirstlane((int)b);
+  K.nch = __builtin_amdgcn_readfirstlane(S.nch);
+  K.nit = __builtin_amdgcn_readfirstlane(S.nit);
+  K.has_map = __builtin_amdgcn_readfirstlane(S.has_map);
+  return K;
+}
+
 // Collision test of nc <= ct configurations q_lds[c], ct in {1, 2, 4, 8}, all block threads.  Configuration c belongs
 // to the G = 8 / ct wavefronts c*G .. c*G + G - 1 (its group): a job tile of one configuration is spread over the whole
 // workgroup instead of one wavefront.  Every wavefront of a group computes the configuration's kinematics, all sphere
@@ -954,11 +1069,11 @@ struct WideLds {
 // after its first hit or once another wavefront of the group reported one.  The caller zeroes L.coll[0 .. ct) before
 // the barrier that publishes q_lds; on return (after a block barrier) L.coll[c] is 1 for the colliding configurations.
 // prof (thread 0): stage clocks A, B, centres + prefilter loads, whole tile, as collide_tile's.
-__device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, const SceneDev& sc_in,
-                                             const MapCfg* __restrict__ mc, int ct, int nc, const double (*q_lds)[NJ],
-                                             int self, int map, WideLds& L, const TileOrder* ord = nullptr,
+__device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, const WideConst& K, int ct, int nc,
+                                             const double (*q_lds)[NJ], int self, int map, WideLds& L,
+                                             const TileOrder* ord = nullptr,
                                              unsigned long long* prof = nullptr, unsigned long long* prof2 = nullptr) {
-  const SceneDev sc = uniform_scene(sc_in);
+  const SceneDev& sc = K.sc;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int G = __builtin_amdgcn_readfirstlane(NWAVE / ct);
   const int c = wave / G, g = wave - c * G;
@@ -969,80 +1084,145 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
   if (live && ord) live = !(ord->ord[c] > ord->first(ord->grp[c]));
   if (__builtin_amdgcn_readfirstlane(live)) {
     const double* q = q_lds[c];
-    const int nch = rb->n_chain;
-    // A: local frame of every chain step (sin/cos included), one lane each
+    const int nch = K.nch;
+    // A: local frame of every chain step (sin/cos included), one lane each.  The step's type and joint are in
+    // registers, so the joint value and the step's constants come in one batch of LDS reads; the revolute, prismatic
+    // and fixed frames are chain_local's expressions, formed side by side and selected by type.
     if (lane < nch) {
-      double st = 0.0, cs = 1.0;
-      if (rb->ch_type[lane] == 1) psincos(q[rb->ch_joint[lane]], &st, &cs);
-      Frame F;
-      chain_local(rb, lane, q, st, cs, &F);
-      double* o = W.u.lf[lane];
-      for (int i = 0; i < 9; ++i) o[i] = F.R[i];
-      o[9] = F.p[0]; o[10] = F.p[1]; o[11] = F.p[2];
+      const int k = lane;
+      const double qq = q[K.a_j];
+      double ax[3], og[3], fR[9], fp[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        ax[d] = rb->ch_axis[k * 3 + d];
+        og[d] = rb->ch_origin[k * 3 + d];
+        fp[d] = rb->ch_p[k * 3 + d];
+      }
+#pragma unroll
+      for (int i = 0; i < 9; ++i) fR[i] = rb->ch_R[k * 9 + i];
+      double st, cs, R1[9];
+      psincos(qq, &st, &cs);
+      rot2_sc(ax, st, cs, R1);
+      const bool rev = K.a_ty == 1, pri = K.a_ty == 2;
+      double* o = W.u.lf[k];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) o[i] = rev ? R1[i] : (pri ? (i % 4 == 0 ? 1.0 : 0.0) : fR[i]);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const double pp = og[d] + ax[d] * qq;
+        o[9 + d] = rev ? og[d] : (pri ? pp : fp[d]);
+      }
     }
     if (lane < (MAX_SPH + 31) / 32) W.cand[lane] = 0u;
     if (lane == 0) W.pcand = 0u;
     wave_sync();
     if (prof && threadIdx.x == 0) ta = wall_clock64();
-    // B: the chain product, one lane per element (rows r = 0..2 of four lanes: columns 0..2 of R, then p), as
-    // collide_tile's stage B (fmul's three-term sums in KDL order; row r of T from the lane's quad by DPP broadcasts)
-    if (lane < 12) {
-      const int r = lane >> 2, col = lane & 3;
+    // B: the chain product, one lane per element: row r of T * L in the four lanes 16 r .. 16 r + 3 (columns 0..2 of R,
+    // then p).  Element (r, col) is row r of T times column col of L -- fmul's three-term sum in its order, p adding
+    // T.p[r] last -- and row r of T comes from the lane's own row of 16 by 64-bit DPP row broadcasts (one instruction
+    // each).  The lane's column of the local frames is read WIDE_AHEAD steps ahead of its use (unconditionally: the rows
+    // past nch exist and are not used), and the steps' bodies are bits of a scalar; a step without a body stores into
+    // the spare row MAX_BODY, and the steps come in groups of four up to nch (a group's steps past nch store there too).
+    // So a step waits for no LDS round trip and takes no branch: three broadcasts, six fp64 operations, a select and a
+    // store.
+    if (lane < 48 && (lane & 15) < 4) {
+      constexpr int WIDE_AHEAD = 6;
+      const int r = lane >> 4, col = lane & 3;
       const int lo = col < 3 ? col : 9, ls = col < 3 ? 3 : 1;
       double v = col < 3 ? (r == col ? 1.0 : 0.0) : (r == 2 ? rb->root_z : 0.0);
-      double l0 = W.u.lf[0][lo], l1 = W.u.lf[0][lo + ls], l2 = W.u.lf[0][lo + 2 * ls];
-      int bd = rb->ch_body[0];
-      const int oidx = col < 3 ? r * 3 + col : 9 + r;
-      for (int k = 0; k < nch; ++k) {
-        const int kn = k + 1 < nch ? k + 1 : k;
-        const double* ln = W.u.lf[kn];
-        const double n0 = ln[lo], n1 = ln[lo + ls], n2 = ln[lo + 2 * ls];
-        const int bdn = rb->ch_body[kn];
-        const double t0v = quad_bcast<0>(v), t1v = quad_bcast<1>(v), t2v = quad_bcast<2>(v);
-        const double s = t0v * l0 + t1v * l1 + t2v * l2;
+      const double* lf = &W.u.lf[0][lo];
+      double l[WIDE_AHEAD][3];
+#pragma unroll
+      for (int k = 0; k < WIDE_AHEAD; ++k) {
+        l[k][0] = lf[k * 12]; l[k][1] = lf[k * 12 + ls]; l[k][2] = lf[k * 12 + 2 * ls];
+      }
+      double* out = &W.v.fr[0][col < 3 ? r * 3 + col : 9 + r];
+      // (the steps' rows are taken from the scalar here, two scalar instructions each: as loop invariants of the
+      // caller's tile loop they would be held in registers it does not have, and reloaded from private memory; to
+      // re-check after a compiler change, see the note at the centres' grid sizes below)
+      unsigned long long bodies = K.bodies;
+      asm volatile("" : "+s"(bodies));
+      auto step = [&](int k) {
+        const int nib = (int)((bodies >> (4 * k)) & 15ull);
+        const int bd = nib ? nib - 1 : MAX_BODY;
+        double* lk = l[k % WIDE_AHEAD];
+        const double s = row_bcast<0>(v) * lk[0] + row_bcast<1>(v) * lk[1] + row_bcast<2>(v) * lk[2];
         const double sp = s + v;
         v = col < 3 ? s : sp;
-        if (bd >= 0) W.v.fr[bd][oidx] = v;
-        l0 = n0; l1 = n1; l2 = n2;
-        bd = bdn;
+        out[bd * 12] = v;
+        if (k + WIDE_AHEAD < MAX_CHAIN) {
+          const int kn = k + WIDE_AHEAD;
+          lk[0] = lf[kn * 12]; lk[1] = lf[kn * 12 + ls]; lk[2] = lf[kn * 12 + 2 * ls];
+        }
+      };
+#pragma unroll
+      for (int k = 0; k < 8; ++k) step(k);
+      if (nch > 8) {
+#pragma unroll
+        for (int k = 8; k < 12; ++k) step(k);
+        if (nch > 12) {
+#pragma unroll
+          for (int k = 12; k < MAX_CHAIN; ++k) step(k);
+        }
       }
     }
     wave_sync();
     if (prof && threadIdx.x == 0) tb = wall_clock64();
     // centres of every sphere and frames of every primitive (the self pairs need them all); the prefilter loads of
-    // this wavefront's share, all issued together
-    const int nsph = rb->n_sph, npr = rb->n_prim;
-    const bool do_map = map && mc->has_map;
+    // this wavefront's share, all issued together.  An item's body, its centre's place in the model and its threshold
+    // are in registers: the body frame, the centre and the x axis come in one batch (a primitive's centre is the same
+    // three-term sums as a sphere's, prim_world).
+    const int nsph = rb->n_sph;
+    const bool do_map = map && K.has_map;
+    const double* rbd = reinterpret_cast<const double*>(rb);
     // (the cells first, then every load -- box-gap bytes of the spheres, slab words of the primitives -- issued before
     // any is used: in a 2 cm scene the 25 MB field lives in the Infinity Cache, and dependent rounds cost ~1 us each)
     long long cell[2], pcell[2];
-    const uint16_t* pslab[2];
+    // (the grid's sizes as doubles, for centre_cell's comparisons: converted here, in three scalar-operand instructions
+    // -- as loop invariants of the caller's tile loop they would be held in vector registers it does not have.  The
+    // empty asm only keeps the conversions here and changes no value; whether a compiler still needs it shows in
+    // helper_main's device assembly: `scratch_` instructions in the tile loop's stages A, B and centres, none now.)
+    int gnx = sc.nx, gny = sc.ny, gnz = sc.nz;
+    asm volatile("" : "+s"(gnx), "+s"(gny), "+s"(gnz));
+    const double fnx = gnx, fny = gny, fnz = gnz;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int it = u * 64 + lane;
       cell[u] = -1;
       pcell[u] = -1;
-      pslab[u] = nullptr;
-      if (it < nsph) {
-        const double* B = W.v.fr[rb->sph_body[it]];
-        const double* p = &rb->sph_cb[it * 3];
+      if (u * 64 >= K.nit) continue;
+      const int kind = K.kind[u] & 3;
+      if (kind) {
+        const double* B = W.v.fr[K.body[u]];
+        double b[12], p[3], a[3];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) b[i] = B[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { p[i] = rbd[K.cb[u] + i]; a[i] = rbd[K.ab + i]; }
         double w[3];
+#pragma unroll
         for (int r = 0; r < 3; ++r) {
-          const double m = B[r * 3 + 0] * p[0] + B[r * 3 + 1] * p[1] + B[r * 3 + 2] * p[2];
-          w[r] = m + B[9 + r];
+          const double m = b[r * 3 + 0] * p[0] + b[r * 3 + 1] * p[1] + b[r * 3 + 2] * p[2];
+          w[r] = m + b[9 + r];
         }
-        W.u.c.wc[it][0] = w[0]; W.u.c.wc[it][1] = w[1]; W.u.c.wc[it][2] = w[2];
-        if (do_map && mc->map_on[it] && it % G == g) cell[u] = centre_cell(sc, w);
-      } else if (it < nsph + npr) {
-        const int p = it - nsph;
-        double pw[5];
-        prim_world(rb, p, W.v.fr[rb->prim_body[p]], pw);
-        for (int i = 0; i < 5; ++i) W.u.c.pw[p][i] = pw[i];
-        if (do_map && mc->p_map_on[p] && p % G == g) {  // prim_candidate: its centre's column, else free
-          const double fx = floor((pw[0] - sc.ox) * sc.inv_res), fy = floor((pw[1] - sc.oy) * sc.inv_res);
-          if (fx >= 0 && fx < sc.nx && fy >= 0 && fy < sc.ny) {
-            pcell[u] = (long long)(int)fy * sc.nx + (int)fx;
-            pslab[u] = sc_in.slab[p];
+        const bool mine = do_map && (K.kind[u] & 4);
+        if (kind == 1) {
+          W.u.c.wc[it][0] = w[0]; W.u.c.wc[it][1] = w[1]; W.u.c.wc[it][2] = w[2];
+          if (mine && it % G == g) {  // centre_cell
+            const double fx = floor((w[0] - sc.ox) * sc.inv_res), fy = floor((w[1] - sc.oy) * sc.inv_res);
+            const double fz = floor((w[2] - sc.oz) * sc.inv_res);
+            if (fx >= 0 && fx < fnx && fy >= 0 && fy < fny && fz >= 0 && fz < fnz)
+              cell[u] = ((long long)(int)fz * sc.ny + (int)fy) * sc.nx + (int)fx;
+          }
+        } else {
+          const int pi = K.prim;
+          double* pw = W.u.c.pw[pi];
+          pw[0] = w[0]; pw[1] = w[1]; pw[2] = w[2];
+          pw[3] = b[0] * a[0] + b[1] * a[1] + b[2] * a[2];
+          pw[4] = b[3] * a[0] + b[4] * a[1] + b[5] * a[2];
+          if (mine && pi % G == g) {  // prim_candidate: its centre's column, else free
+            const double fx = floor((w[0] - sc.ox) * sc.inv_res), fy = floor((w[1] - sc.oy) * sc.inv_res);
+            if (fx >= 0 && fx < fnx && fy >= 0 && fy < fny) pcell[u] = (long long)(int)fy * sc.nx + (int)fx;
           }
         }
       }
@@ -1051,23 +1231,26 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       dv[u] = cell[u] < 0 ? 0xffffffffu : (sc.d2b ? (uint32_t)sc.d2b[cell[u]] : (uint32_t)sc.d2[cell[u]]);
-      sv[u] = pcell[u] < 0 ? 0xffffffffu : (uint32_t)pslab[u][pcell[u]];
+      sv[u] = pcell[u] < 0 ? 0xffffffffu : (uint32_t)K.slab[pcell[u]];
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int it = u * 64 + lane;
-      if (cell[u] >= 0 && dv[u] <= mc->T[it]) atomicOr(&W.cand[it >> 5], 1u << (it & 31));
-      if (pcell[u] >= 0 && sv[u] <= mc->pT[it - nsph]) atomicOr(&W.pcand, 1u << (it - nsph));
+      if (cell[u] >= 0 && dv[u] <= K.T[u]) atomicOr(&W.cand[it >> 5], 1u << (it & 31));
+      if (pcell[u] >= 0 && sv[u] <= K.T[u]) atomicOr(&W.pcand, 1u << K.prim);
     }
     wave_sync();
     if (prof && threadIdx.x == 0) tc = wall_clock64();
-    // map: this wavefront's candidate primitives, then its candidate spheres (their brick words in one round trip)
+    // map: this wavefront's candidate primitives, then its candidate spheres (their brick words in one round trip).
+    // Another wavefront of the group may have reported a hit meanwhile (G > 1 only: with one wavefront per
+    // configuration nobody else writes L.coll[c]).
     bool hit = false;
     unsigned long long tp0 = (prof2 && threadIdx.x == 0) ? wall_clock64() : 0, tp1 = tp0, tp2 = tp0;
     for (uint32_t pm = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.pcand); pm && !hit;) {
       const int p = __builtin_ctz(pm);
       pm &= pm - 1;
-      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))
+      if (G > 1 &&
+          __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))
         break;
       const double pw[5] = {W.u.c.pw[p][0], W.u.c.pw[p][1], W.u.c.pw[p][2], W.u.c.pw[p][3], W.u.c.pw[p][4]};
       hit = wave_prim_map(sc, rb->prim_type[p], &rb->prim_h[p * 3], pw, lane);
@@ -1076,13 +1259,15 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
     uint32_t any = 0;
     for (int wd = 0; wd < (MAX_SPH + 31) / 32; ++wd) any |= W.cand[wd];
     if (!hit && __builtin_amdgcn_readfirstlane((int)(any != 0)) &&
-        !__builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))
+        !(G > 1 &&
+          __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))))
       hit = wave_map_staged<WIDE_STAGE_W, uint16_t>(rb, sc, W.u.c.wc, W.cand, nsph, W.stage, W.owner, W.off, lane,
                                                     W.list);
     if (prof2 && threadIdx.x == 0) tp2 = wall_clock64();
     // self: this wavefront's 64-pair chunks of the sphere pairs, then of the (primitive, sphere) pairs
     if (self && !hit &&
-        !__builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) {
+        !(G > 1 &&
+          __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))) {
       const int nsp = rb->n_spairs, npp = rb->n_ppairs, ks = (nsp + 63) >> 6;
       bool sh = false;
 #pragma unroll 4

@@ -33,6 +33,9 @@ constexpr int CHECK_CT = 32;
 // Robot model and map configuration staged in LDS by every kernel that runs collision tiles.
 __shared__ RobotDev g_rb;
 __shared__ MapCfg g_mc;
+// The per-lane constants of the job tiles (WideConst) of a workgroup that publishes jobs and runs a tile of its own now
+// and then (plan_kernel's leaders and scouts): filled once per launch, read back by job_tile_mask_out.
+__shared__ WideStash g_wk;
 
 // Copies the robot model and the map configuration into LDS (read by every collision stage).
 __device__ __forceinline__ void stage_model(const RobotDev* rb, const MapCfg* mc, RobotDev* rbl, MapCfg* mcl) {
@@ -83,6 +86,7 @@ __global__ void __launch_bounds__(BLOCK) check_wide_kernel(const RobotDev* __res
   unsigned long long c0 = 0, w0 = 0;
   if (pr && threadIdx.x == 0) { c0 = __builtin_amdgcn_s_memtime(); w0 = wall_clock64(); }
   stage_model(rb, mc, &g_rb, &g_mc);
+  const WideConst K = wide_const(&g_rb, sc, &g_mc);  // once per workgroup, for all its tiles
   const long long ntiles = (n + ct - 1) / ct;
   for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const long long base = t * ct;
@@ -93,7 +97,7 @@ __global__ void __launch_bounds__(BLOCK) check_wide_kernel(const RobotDev* __res
     }
     if (threadIdx.x < TILE_CT_MAX) L.coll[threadIdx.x] = 0;
     __syncthreads();
-    collide_wide(&g_rb, sc, &g_mc, ct, nc, ql, self, map, L, nullptr, pr, pr ? pr + 6 : nullptr);
+    collide_wide(&g_rb, K, ct, nc, ql, self, map, L, nullptr, pr, pr ? pr + 6 : nullptr);
     if (threadIdx.x < nc) valid[base + threadIdx.x] = L.coll[threadIdx.x] ? 0 : 1;
     __syncthreads();
   }
@@ -2348,30 +2352,67 @@ __device__ __forceinline__ bool job_tile_skip(const Ctx& C, JobLds& J, int t, in
 // Configurations of job tile t -> J.tq: slot s = job edge s / np1, point s % np1, configuration start + i * step
 // (the leader's arithmetic).  Then the collision tile; returns the tile's collision mask in every thread.
 // `seq` >= 0 in skip mode: configurations skipped by job_tile_skip report no collision.
-__device__ __forceinline__ unsigned job_tile_mask(const Ctx& C, JobLds& J, int t, unsigned long long* prof = nullptr,
-                                                  int seq = -1) {
-  const int ct = uni(J.ct), base = t * ct, nc = min(ct, uni(J.nslots) - base);
-  const bool sk = seq >= 0 && uni(J.skip) && t >= uni(C.Q.nworkers);
-  if (sk && job_tile_skip(C, J, t, seq)) return 0u;
-  if (threadIdx.x < nc * NJ) {
-    const int c = threadIdx.x / NJ, j = threadIdx.x - c * NJ;
-    const int sl = base + c, k = sl / J.np1, i = sl - k * J.np1;
-    J.tq[c][j] = J.start[k][j] + i * J.step[k][j];
+// `direct` (a helper's first tile of a job, never in skip mode; block-uniform): the job's decoded fields in J may not
+// be published yet, so the header fields come from the job's header word and every wavefront forms its own
+// configuration from the payload words in J.words -- the same start + i * step -- and starts the tile without a block
+// barrier; J.T.coll was cleared before the barrier that published J.words.  Then the barrier that ends the tile is left
+// to the caller, who stores the result first.
+struct DirectJob {
+  unsigned hdr;  // the payload's header word (J.words[0])
+  int ne;        // its edges
+};
+__device__ __forceinline__ unsigned job_tile_mask(const Ctx& C, const WideConst& K, JobLds& J, int t,
+                                                  unsigned long long* prof = nullptr, int seq = -1,
+                                                  const DirectJob* direct = nullptr, bool sync_after = true) {
+  int ct, nc, self, map;
+  bool sk = false;
+  if (direct) {
+    const unsigned hdr = direct->hdr;
+    const int ne = direct->ne;
+    const int np1 = (int)((hdr >> 8) & 255);
+    ct = 1 << ((hdr >> 21) & 3);
+    const int base = t * ct;
+    nc = min(ct, ne * np1 - base);
+    self = (int)((hdr >> 16) & 1);
+    map = (int)((hdr >> 17) & 1);
+    const int c = (int)(threadIdx.x >> 6) / (NWAVE / ct), j = threadIdx.x & 63;
+    if (c < nc && j < NJ) {  // (the wavefronts of a configuration's group store the same values)
+      const int sl = base + c, k = sl / np1, i = sl - k * np1, wi = 1 + 32 * k + 2 * j;
+      const double qs = __hiloint2double((int)J.words[wi + 1], (int)J.words[wi]);
+      const double qd = __hiloint2double((int)J.words[wi + 2 * NJ + 1], (int)J.words[wi + 2 * NJ]);
+      J.tq[c][j] = qs + i * qd;
+    }
+    wave_sync();
+  } else {
+    ct = uni(J.ct);
+    const int base = t * ct;
+    nc = min(ct, uni(J.nslots) - base);
+    self = J.self;
+    map = J.map;
+    sk = seq >= 0 && uni(J.skip) && t >= uni(C.Q.nworkers);
+    if (sk && job_tile_skip(C, J, t, seq)) return 0u;
+    if (threadIdx.x < nc * NJ) {
+      const int c = threadIdx.x / NJ, j = threadIdx.x - c * NJ;
+      const int sl = base + c, k = sl / J.np1, i = sl - k * J.np1;
+      J.tq[c][j] = J.start[k][j] + i * J.step[k][j];
+    }
+    if (threadIdx.x < TILE_CT_MAX) J.T.coll[threadIdx.x] = 0;
+    __syncthreads();
   }
-  if (threadIdx.x < TILE_CT_MAX) J.T.coll[threadIdx.x] = 0;
-  __syncthreads();
   const TileOrder order{J.tgrp, J.tord, J.first, false};
-  collide_wide((&g_rb), C.sc, (&g_mc), ct, nc, J.tq, J.self, J.map, J.T, sk ? &order : nullptr, prof);
+  collide_wide((&g_rb), K, ct, nc, J.tq, self, map, J.T, sk ? &order : nullptr, prof);
   unsigned m = 0;
   for (int c = 0; c < nc; ++c) m |= (J.T.coll[c] ? 1u : 0u) << c;
-  __syncthreads();
+  if (sync_after) __syncthreads();  // (else the caller's, before anything of the next tile is written)
   return m;
 }
 
 // job_tile_mask as a call, for the publisher's own and stolen tiles (rare while it has helpers): the collision tile's
 // registers and code stay out of edge_validity and of the workgroups that inline it (the scouts).
+// Its WideConst comes from the workgroup's LDS copy (g_wk, filled once per launch by plan_kernel), not from the model.
 __device__ __noinline__ unsigned job_tile_mask_out(const Ctx& C, JobLds& J, int t, int seq) {
-  return job_tile_mask(C, J, t, nullptr, seq);
+  const WideConst K = wide_const_load(g_wk, C.sc);
+  return job_tile_mask(C, K, J, t, nullptr, seq);
 }
 
 // Work the leader does while a collision job's tiles are checked by the helpers (see edge_validity).
@@ -3003,6 +3044,7 @@ __device__ __noinline__ void helper_main(const Ctx& C, int hidx, JobLds& J) {
   constexpr int PU = SMP_POLL_N / 64;
   static_assert(PU >= 1 && PU * 64 <= JOB_WORDS, "poll width");
   static_assert(SCAN_WORDS <= 64, "a scan payload is one granule per lane");
+  const WideConst K = wide_const(&g_rb, C.sc, &g_mc);  // this lane's model and scene constants, for every tile it runs
   for (int k = 0;; k ^= 1) {
     // 0 = nothing new, > 0 = collision job number complete in J.words, -1 = leave, -2 = collision payload longer than
     // the poll, -3 = scan job complete in J.words
@@ -3034,6 +3076,8 @@ __device__ __noinline__ void helper_main(const Ctx& C, int hidx, JobLds& J) {
           go = nw <= PU * 64 ? (int)tag0 : -2;
         }
       }
+      // (a job's first tile starts without a further barrier, see below: its collision flags are cleared here)
+      if (go > 0 && threadIdx.x < TILE_CT_MAX) J.T.coll[threadIdx.x] = 0;
       if (threadIdx.x == 0) {
         if (go == 0 && (ld_agent(&jb->stop) || wall_clock64() - t_last > 200000000ull)) go = -1;  // 2 s idle
         J.go[k] = go;
@@ -3071,44 +3115,66 @@ __device__ __noinline__ void helper_main(const Ctx& C, int hidx, JobLds& J) {
       __syncthreads();
       if (uni(J.left)) continue;
     }
-    for (int it = threadIdx.x; it < ne * 2 * NJ; it += BLOCK) {
-      const int kk = it / (2 * NJ), r = it - kk * 2 * NJ;  // r < NJ: start[j], else step[j - NJ]
-      const int wi = 1 + 32 * kk + 2 * r;
-      const double d = __hiloint2double((int)J.words[wi + 1], (int)J.words[wi]);
-      if (r < NJ) J.start[kk][r] = d; else J.step[kk][r - NJ] = d;
-    }
-    if (threadIdx.x == 0) {
-      J.E = ne;
-      J.np1 = (int)((hdr >> 8) & 255);
-      J.self = (hdr >> 16) & 1;
-      J.map = (hdr >> 17) & 1;
-      J.skip = (hdr >> 19) & 1;
-      J.sfv = (hdr >> 20) & 1;
-      J.nslots = ne * J.np1;
-      J.ct = 1 << ((hdr >> 21) & 3);
-      J.ntiles = (J.nslots + J.ct - 1) / J.ct;
-    }
-    if (hdr & (1u << 19))
-      for (int t = threadIdx.x; t < JOB_TILES; t += BLOCK) J.rdone[t] = 0;
-    __syncthreads();
-    last = seq;
-    const int nt = uni(J.ntiles);
-#ifdef SMP_JOB_PROF
-    if (threadIdx.x == 0 && w - 1 < nt) {
-      const unsigned long long tp = ld_agent(&jb->dbg[0]);
-      atomicAdd(&jb->dbg[1], wall_clock64() - tp);
-      atomicAdd(&jb->dbg[2], 1ull);
-    }
-#endif
+    // the job's edges and header fields -> J (all threads; the caller's barrier publishes them)
+    auto decode = [&]() {
+      for (int it = threadIdx.x; it < ne * 2 * NJ; it += BLOCK) {
+        const int kk = it / (2 * NJ), r = it - kk * 2 * NJ;  // r < NJ: start[j], else step[j - NJ]
+        const int wi = 1 + 32 * kk + 2 * r;
+        const double d = __hiloint2double((int)J.words[wi + 1], (int)J.words[wi]);
+        if (r < NJ) J.start[kk][r] = d; else J.step[kk][r - NJ] = d;
+      }
+      if (threadIdx.x == 0) {
+        J.E = ne;
+        J.np1 = (int)((hdr >> 8) & 255);
+        J.self = (hdr >> 16) & 1;
+        J.map = (hdr >> 17) & 1;
+        J.skip = (hdr >> 19) & 1;
+        J.sfv = (hdr >> 20) & 1;
+        J.nslots = ne * J.np1;
+        J.ct = 1 << ((hdr >> 21) & 3);
+        J.ntiles = (J.nslots + J.ct - 1) / J.ct;
+      }
+      if (hdr & (1u << 19))
+        for (int t = threadIdx.x; t < JOB_TILES; t += BLOCK) J.rdone[t] = 0;
+    };
 #ifdef SMP_JOB_PROF
     if (threadIdx.x == 0) for (int i = 0; i < 4; ++i) J.tprof[i] = 0;
     unsigned long long* tp = J.tprof;
 #else
     unsigned long long* tp = nullptr;
 #endif
+    // This helper's first tile (w - 1; never in skip mode, which begins with a worker's second tile) goes straight from
+    // the payload when the poll brought all of it (job_tile_mask, `direct`): it waits neither for the decode nor for
+    // J.tq at two block barriers.  The decode is left to the helper's second tile of the job, which most jobs do not
+    // have (the payload words stay in J.words until the next poll).
+    const int nt = (ne * (int)((hdr >> 8) & 255) + (1 << ((hdr >> 21) & 3)) - 1) >> ((hdr >> 21) & 3);  // = J.ntiles
+    const bool direct = go > 0;
+    last = seq;
+#ifdef SMP_JOB_PROF
+    if (threadIdx.x == 0 && w - 1 < nt) {
+      const unsigned long long tpk = ld_agent(&jb->dbg[0]);
+      atomicAdd(&jb->dbg[1], wall_clock64() - tpk);
+      atomicAdd(&jb->dbg[2], 1ull);
+    }
+#endif
+    // Every wavefront has read J.seq and J.words[0] above, and wave 0's next poll rewrites both: a block barrier must
+    // lie between.  A helper with a tile of this job meets one in the tile; one without (most helpers of a small job:
+    // idle, off the job's critical path) takes it here.  Without it a slow wavefront could read the next job's header,
+    // count another nt and part from the others at a barrier.
+    if (w - 1 >= nt) __syncthreads();
+    bool decoded = false;
+    const DirectJob dj{hdr, ne};
     for (int t = w - 1; t < nt; t += W) {
-      const unsigned m = job_tile_mask(C, J, t, tp, seq);
+      const bool dt = direct && t == w - 1;
+      if (!dt && !decoded) {
+        decode();
+        __syncthreads();
+        decoded = true;
+      }
+      // (the result goes out before the tile's last barrier, not after it: the publisher is waiting for it)
+      const unsigned m = job_tile_mask(C, K, J, t, tp, seq, dt ? &dj : nullptr, false);
       if (threadIdx.x == 0) st_agent(&jb->res[t], granule(seq, m));
+      __syncthreads();
 #ifdef SMP_JOB_PROF
       if (threadIdx.x == 0) atomicAdd(&jb->dbg[3], wall_clock64() - ld_agent(&jb->dbg[0]));
 #endif
@@ -6159,6 +6225,9 @@ __global__ void __launch_bounds__(BLOCK) plan_kernel(const RobotDev* __restrict_
   }
   stage_model(rb, mc, &g_rb, &g_mc);  // (ends with a barrier)
   Ctx& C = g_ctx;
+  // the job tiles' per-lane constants, once per launch, for this workgroup's own and stolen tiles (job_tile_mask_out)
+  wide_const_store(g_wk, wide_const(&g_rb, C.sc, &g_mc));
+  __syncthreads();
   if (srole >= 0) {
     if (srole < C.Q.nscouts) scout_main(C, srole);  // one call site: inlined
     return;
