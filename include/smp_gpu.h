@@ -175,6 +175,14 @@ int smp_robot_create_urdf(const char* urdf_xml, const char* srdf_xml, const char
 void smp_robot_destroy(smp_robot* r);
 int smp_robot_num_links(const smp_robot* r);
 const char* smp_robot_link_name(const smp_robot* r, int i);
+/* The model's self-collision lists and the round schedule of the job tiles' self test (read only).
+ * info: n_sph, n_prim, n_spairs, n_ppairs, qualifies (1: the job tiles run the rounds, 0: the flat lists), rounds,
+ * lanes, max_rounds.  Every array may be NULL: sp_ab[n_spairs] (a | b << 8) and sp_rr2[n_spairs], the flat sphere
+ * pairs and their thresholds; pp_ps[n_ppairs] (primitive | sphere << 8); partner / rr2 [lanes * max_rounds], slot
+ * lane * max_rounds + round: the other sphere of the pair that sphere `lane` owns in that round (-1: none) and the
+ * threshold the tile forms for it, (r_lane + r_partner)^2; prim_mask[n_sph]: bit p set iff sphere s is paired with primitive p. */
+int smp_robot_self_rounds(const smp_robot* r, int32_t info[8], uint16_t* sp_ab, double* sp_rr2, uint16_t* pp_ps,
+                          int32_t* partner, double* rr2, uint32_t* prim_mask);
 
 int smp_scene_from_keys(const uint16_t* keys_xyz, int64_t n, const smp_scene_opts* opts, smp_scene** out);
 int smp_scene_from_bt(const uint8_t* data, size_t size, const smp_scene_opts* opts, smp_scene** out);

@@ -102,6 +102,7 @@ EXPORTS = [
     ("smp_robot_destroy", None, [_p]),
     ("smp_robot_num_links", _i, [_p]),
     ("smp_robot_link_name", ctypes.c_char_p, [_p, _i]),
+    ("smp_robot_self_rounds", _i, [_p, _p, _p, _p, _p, _p, _p, _p]),
     ("smp_scene_from_keys", _i, [_p, _i64, ctypes.POINTER(SceneOpts), ctypes.POINTER(_p)]),
     ("smp_scene_from_bt", _i, [_p, ctypes.c_size_t, ctypes.POINTER(SceneOpts), ctypes.POINTER(_p)]),
     ("smp_scene_from_ot", _i, [_p, ctypes.c_size_t, ctypes.POINTER(SceneOpts), ctypes.POINTER(_p)]),

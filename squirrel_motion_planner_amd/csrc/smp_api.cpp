@@ -286,6 +286,28 @@ const char* smp_robot_link_name(const smp_robot* r, int i) {
   if (!r || i < 0 || i >= (int)r->h.link_names.size()) return nullptr;
   return r->h.link_names[i].c_str();
 }
+int smp_robot_self_rounds(const smp_robot* r, int32_t info[8], uint16_t* sp_ab, double* sp_rr2, uint16_t* pp_ps,
+                          int32_t* partner, double* rr2, uint32_t* prim_mask) {
+  if (!r || !info) return SMP_ERR_ARG;
+  const RobotDev& d = r->h.dev;
+  const int32_t v[8] = {d.n_sph, d.n_prim, d.n_spairs, d.n_ppairs, d.sr_ok, d.sr_rounds, SR_LANES, MAX_SROUNDS};
+  std::memcpy(info, v, sizeof(v));
+  if (sp_ab) std::memcpy(sp_ab, d.sp_ab, d.n_spairs * sizeof(uint16_t));
+  if (sp_rr2) std::memcpy(sp_rr2, d.sp_rr2, d.n_spairs * sizeof(double));
+  if (pp_ps) std::memcpy(pp_ps, d.pp_ps, d.n_ppairs * sizeof(uint16_t));
+  for (int l = 0; l < SR_LANES; ++l)
+    for (int k = 0; k < MAX_SROUNDS; ++k) {
+      // (an empty slot holds the lane itself; the threshold is what the tile forms: the two radii's sum, squared)
+      const int o = d.sr_partner[l][k];
+      const bool used = d.sr_ok && o != l;
+      volatile double rs = used ? d.sph_r[l] + d.sph_r[o] : 0.0;
+      if (partner) partner[l * MAX_SROUNDS + k] = used ? o : -1;
+      if (rr2) rr2[l * MAX_SROUNDS + k] = used ? rs * rs : -1.0;
+    }
+  if (prim_mask)
+    for (int s = 0; s < d.n_sph; ++s) prim_mask[s] = d.sph_pmask[s];
+  return SMP_OK;
+}
 
 int smp_scene_from_keys(const uint16_t* keys, int64_t n, const smp_scene_opts* o, smp_scene** out) {
   if (!o || !out || (n > 0 && !keys) || !(o->resolution > 0)) return SMP_ERR_ARG;
@@ -429,6 +451,10 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
       }
     }
   }
+  // SMP_SELF_FLAT: the job tiles of this planner run the flat self-pair lists, as for a model that does not qualify
+  // for the rounds (experiments, and the parity test of the two forms); the planner's copy of the model only
+  if (const char* e = std::getenv("SMP_SELF_FLAT"))
+    if (std::atoi(e) != 0) p->robot.dev.sr_ok = 0;
   // every failure from here on releases what was created so far (smp_planner_destroy skips null handles)
   if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&p->d_rb, sizeof(RobotDev)) != hipSuccess || hipMalloc(&p->d_mc, sizeof(MapCfg)) != hipSuccess ||

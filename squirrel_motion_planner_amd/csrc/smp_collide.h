@@ -959,6 +959,7 @@ struct WideLds {
 struct WideConst {
   SceneDev sc;                  // scalars and field pointers in scalar registers (slab[] is not copied: `slab` below)
   int nch, nit, has_map;        // chain steps; items (spheres + primitives); a scene is present
+  int sr;                       // self test in rounds: sr_ok | sr_rounds << 8 | n_prim << 16 | prim_cyl << 24
   unsigned long long bodies;    // chain step k: its body + 1 in bits 4k .. 4k + 3, 0 = none (MAX_BODY <= 15)
   int a_ty, a_j;                // stage A, lane k < nch: type of chain step k and its joint (0 for a fixed step)
   // centres, item u * 64 + lane: 0 none, 1 sphere, 2 primitive, | 4 if it is tested against the map; its body; the
@@ -984,6 +985,8 @@ __device__ __forceinline__ WideConst wide_const(const RobotDev* __restrict__ rb,
   K.nch = __builtin_amdgcn_readfirstlane(rb->n_chain);
   K.nit = nsph + npr;
   K.has_map = __builtin_amdgcn_readfirstlane(mc->has_map);
+  K.sr = __builtin_amdgcn_readfirstlane((rb->sr_ok & 1) | (rb->sr_rounds & 0xff) << 8 | (npr & 0xff) << 16 |
+                                        (int)((unsigned)rb->prim_cyl << 24));
   unsigned long long bodies = 0;
   for (int k = 0; k < K.nch; ++k)
     bodies |= (unsigned long long)(unsigned)(__builtin_amdgcn_readfirstlane(rb->ch_body[k]) + 1) << (4 * k);
@@ -1029,7 +1032,7 @@ struct WideStash {
     const uint16_t* slab;
   } lane[64];
   unsigned long long bodies;
-  int nch, nit, has_map;
+  int nch, nit, has_map, sr;
 };
 // Stores K (any wavefront's) into S.  Threads 0..63; the caller's barrier publishes it.
 __device__ __forceinline__ void wide_const_store(WideStash& S, const WideConst& K) {
@@ -1039,7 +1042,7 @@ __device__ __forceinline__ void wide_const_store(WideStash& S, const WideConst& 
     for (int u = 0; u < 2; ++u) { l.kind[u] = K.kind[u]; l.body[u] = K.body[u]; l.cb[u] = K.cb[u]; l.T[u] = K.T[u]; }
     l.ab = K.ab; l.prim = K.prim; l.slab = K.slab;
   }
-  if (threadIdx.x == 0) { S.bodies = K.bodies; S.nch = K.nch; S.nit = K.nit; S.has_map = K.has_map; }
+  if (threadIdx.x == 0) { S.bodies = K.bodies; S.nch = K.nch; S.nit = K.nit; S.has_map = K.has_map; S.sr = K.sr; }
 }
 // The WideConst of this wavefront from S: one batch of LDS reads at addresses known from the lane number.
 __device__ __forceinline__ WideConst wide_const_load(const WideStash& S, const SceneDev& sc_in) {
@@ -1055,6 +1058,7 @@ __device__ __forceinline__ WideConst wide_const_load(const WideStash& S, const S
   K.nch = __builtin_amdgcn_readfirstlane(S.nch);
   K.nit = __builtin_amdgcn_readfirstlane(S.nit);
   K.has_map = __builtin_amdgcn_readfirstlane(S.has_map);
+  K.sr = __builtin_amdgcn_readfirstlane(S.sr);
   return K;
 }
 
@@ -1264,30 +1268,105 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
       hit = wave_map_staged<WIDE_STAGE_W, uint16_t>(rb, sc, W.u.c.wc, W.cand, nsph, W.stage, W.owner, W.off, lane,
                                                     W.list);
     if (prof2 && threadIdx.x == 0) tp2 = wall_clock64();
-    // self: this wavefront's 64-pair chunks of the sphere pairs, then of the (primitive, sphere) pairs
+    // self: this wavefront's share of the sphere pairs, then of the (primitive, sphere) pairs -- in rounds for a model
+    // with one item per lane, else in 64-pair chunks of the flat lists
     if (self && !hit &&
         !(G > 1 &&
           __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))) {
-      const int nsp = rb->n_spairs, npp = rb->n_ppairs, ks = (nsp + 63) >> 6;
       bool sh = false;
-#pragma unroll 4
-      for (int k = g; k < ks; k += G) {
-        const int p = k * 64 + lane;
-        if (p < nsp) {
-          const uint32_t ab = rb->sp_ab[p];
-          const double* wa = W.u.c.wc[ab & 0xff];
-          const double* wb = W.u.c.wc[ab >> 8];
-          const double ex = wa[0] - wb[0], ey = wa[1] - wb[1], ez = wa[2] - wb[2];
-          sh |= ex * ex + ey * ey + ez * ez <= rb->sp_rr2[p];
+      if ((K.sr & 1) && G < NWAVE) {
+        // in rounds (RobotDev::sr_*; the counts and the primitives' types are bits of the scalar K.sr, so nothing is
+        // waited for before the first loads): the lane owns sphere `lane` -- its centre, radius, primitive mask and
+        // row of partners come in one batch at addresses known from the lane number, with the first primitives' half
+        // extents and frames (broadcast reads).  Round r tests the sphere against its r-th partner: one gathered
+        // centre and radius, the threshold (r_own + r_partner)^2 formed as sp_rr2 is, and the flat form's sum of
+        // squares (own - partner may be a - b or b - a: exact negations, the same squares).  A group's loads are all
+        // issued before the first is used.  The wavefronts of a group take the rounds r with r % G == g; a group's
+        // rounds past the table's end are clamped to it (they repeat a round), and a round past the model's count
+        // holds empty slots only.  One configuration over all eight wavefronts (G = 8) keeps the flat chunks: a
+        // wavefront's share is then one round and one primitive, and the batch of the lane's own values in front of
+        // them costs more than the share saves (measured: 5.6 -> 5.8 us per tile, against 7.3 -> 6.7 at G = 2).
+        const int nr = (K.sr >> 8) & 0xff, npr = (K.sr >> 16) & 0xff;
+        const uint32_t cyl = (uint32_t)K.sr >> 24;
+        if (lane < nsph) {
+          constexpr int SR_GROUP = 5, PR_GROUP = 2;
+          static_assert(MAX_SROUNDS == 16, "a lane's partners in one 16-byte read");
+          const double* wo = W.u.c.wc[lane];
+          const double own[3] = {wo[0], wo[1], wo[2]};
+          const double ro = rb->sph_r[lane];
+          const uint32_t pmask = rb->sph_pmask[lane];
+          const uint4 row = *reinterpret_cast<const uint4*>(rb->sr_partner[lane]);
+          // (the primitives' numbers continue after the sphere rounds', so that G > nr wavefronts share them; a
+          // number past the model's count reads the last row and its result is dropped)
+          int p0 = (g - nr % G + G) % G;
+          double h[PR_GROUP][3], pw[PR_GROUP][5];
+          auto prim_loads = [&]() {
+#pragma unroll
+            for (int i = 0; i < PR_GROUP; ++i) {
+              const int p = min(p0 + i * G, MAX_PRIM - 1);
+#pragma unroll
+              for (int d = 0; d < 3; ++d) h[i][d] = rb->prim_h[p * 3 + d];
+#pragma unroll
+              for (int d = 0; d < 5; ++d) pw[i][d] = W.u.c.pw[p][d];
+            }
+          };
+          prim_loads();
+          for (int r0 = g; r0 < nr; r0 += SR_GROUP * G) {
+            double px[SR_GROUP], py[SR_GROUP], pz[SR_GROUP], pr[SR_GROUP];
+            bool ok[SR_GROUP];
+#pragma unroll
+            for (int i = 0; i < SR_GROUP; ++i) {
+              const int r = min(r0 + i * G, MAX_SROUNDS - 1);
+              const uint32_t wd = r < 8 ? (r < 4 ? row.x : row.y) : (r < 12 ? row.z : row.w);
+              const int o = (int)((wd >> ((r & 3) * 8)) & 0xffu);
+              ok[i] = o != lane;  // (an empty slot holds the lane itself)
+              const double* wp = W.u.c.wc[o];
+              px[i] = wp[0]; py[i] = wp[1]; pz[i] = wp[2];
+              pr[i] = rb->sph_r[o];
+            }
+#pragma unroll
+            for (int i = 0; i < SR_GROUP; ++i) {
+              const double ex = own[0] - px[i], ey = own[1] - py[i], ez = own[2] - pz[i];
+              const double rs = ro + pr[i];
+              sh |= ok[i] & (ex * ex + ey * ey + ez * ez <= rs * rs);
+            }
+          }
+          // the primitives, wave-uniform: the type is a bit of the scalar, so sphere_prim's branch is uniform (a
+          // cylinder's square root is issued in the cylinders' rounds only); the lanes whose sphere is paired with
+          // primitive p keep the result
+          while (p0 < npr) {
+#pragma unroll
+            for (int i = 0; i < PR_GROUP; ++i) {
+              const int p = p0 + i * G;
+              if (p < npr) sh |= sphere_prim(((cyl >> p) & 1u) ? 2 : 1, h[i], pw[i], own, ro) & (bool)((pmask >> p) & 1u);
+            }
+            p0 += PR_GROUP * G;
+            if (p0 < npr) prim_loads();
+          }
         }
-      }
-      // chunk numbers continue after the sphere pairs', so that G > ks wavefronts share the primitive pairs
-      for (int k = (g - ks % G + G) % G; k * 64 < npp; k += G) {
-        const int p = k * 64 + lane;
-        if (p < npp) {
-          const uint32_t ps = rb->pp_ps[p];
-          const int pr = ps & 0xff, sp = ps >> 8;
-          sh |= sphere_prim(rb->prim_type[pr], &rb->prim_h[pr * 3], W.u.c.pw[pr], W.u.c.wc[sp], rb->sph_r[sp]);
+      } else {
+        // the flat lists (a model with more than one item per lane or more rounds than the table holds, SMP_SELF_FLAT,
+        // G = 8)
+        const int nsp = rb->n_spairs, npp = rb->n_ppairs, ks = (nsp + 63) >> 6;
+#pragma unroll 4
+        for (int k = g; k < ks; k += G) {
+          const int p = k * 64 + lane;
+          if (p < nsp) {
+            const uint32_t ab = rb->sp_ab[p];
+            const double* wa = W.u.c.wc[ab & 0xff];
+            const double* wb = W.u.c.wc[ab >> 8];
+            const double ex = wa[0] - wb[0], ey = wa[1] - wb[1], ez = wa[2] - wb[2];
+            sh |= ex * ex + ey * ey + ez * ez <= rb->sp_rr2[p];
+          }
+        }
+        // chunk numbers continue after the sphere pairs', so that G > ks wavefronts share the primitive pairs
+        for (int k = (g - ks % G + G) % G; k * 64 < npp; k += G) {
+          const int p = k * 64 + lane;
+          if (p < npp) {
+            const uint32_t ps = rb->pp_ps[p];
+            const int pr = ps & 0xff, sp = ps >> 8;
+            sh |= sphere_prim(rb->prim_type[pr], &rb->prim_h[pr * 3], W.u.c.pw[pr], W.u.c.wc[sp], rb->sph_r[sp]);
+          }
         }
       }
       hit = __ballot(sh) != 0;

@@ -7,6 +7,7 @@
 #include <limits>
 #include <map>
 #include <stdexcept>
+#include <vector>
 
 #include "smp_json.h"
 
@@ -17,6 +18,8 @@ static int type_code(const std::string& t) {
   if (t == "TransAxis") return 2;
   return 0;
 }
+
+static void self_rounds(RobotDev* dp);
 
 static void copy3(const json::Value& v, double* o, int n = 3) {
   if (v.size() != (size_t)n) throw std::runtime_error("model: bad vector length");
@@ -169,6 +172,79 @@ void finish_pairs(RobotDev* dp) {
         d.n_spairs++;
       }
   }
+  self_rounds(dp);
+}
+
+// The round schedule of the sphere pairs (RobotDev::sr_*): every pair is given to one of its two spheres so that the
+// largest number of pairs a sphere owns is as small as possible -- greedily to the sphere that owns fewer (the pair's
+// a on a tie), then, while a sphere with the largest count reaches one with at least two fewer along pairs it and its
+// successors own (breadth first, spheres and pairs in index order), every pair of that path changes hands, which
+// takes one pair off the first sphere and adds one to the last.  No such path from any largest sphere left is the
+// optimum of this orientation problem.  A sphere's pairs, in the flat list's order, are its rounds.
+static void self_rounds(RobotDev* dp) {
+  RobotDev& d = *dp;
+  d.sr_ok = 0;
+  d.sr_rounds = 0;
+  std::memset(d.sr_partner, 0, sizeof(d.sr_partner));
+  std::memset(d.sph_pmask, 0, sizeof(d.sph_pmask));
+  d.prim_cyl = 0;
+  d.sr_pad = 0;
+  for (int p = 0; p < d.n_prim; ++p) d.prim_cyl |= (d.prim_type[p] == 2) << p;
+  for (int p = 0; p < d.n_ppairs; ++p) d.sph_pmask[d.pp_ps[p] >> 8] |= (uint8_t)(1u << (d.pp_ps[p] & 0xff));
+  const int ns = d.n_sph, np = d.n_spairs;
+  if (ns + d.n_prim > SR_LANES) return;
+  std::vector<int> owner(np), cnt(ns, 0);
+  auto sa = [&](int p) { return (int)(d.sp_ab[p] & 0xff); };
+  auto sb = [&](int p) { return (int)(d.sp_ab[p] >> 8); };
+  for (int p = 0; p < np; ++p) {
+    owner[p] = cnt[sb(p)] < cnt[sa(p)] ? sb(p) : sa(p);
+    cnt[owner[p]]++;
+  }
+  std::vector<std::vector<int>> inc(ns);  // pairs of every sphere
+  for (int p = 0; p < np; ++p) { inc[sa(p)].push_back(p); inc[sb(p)].push_back(p); }
+  for (bool moved = true; moved;) {
+    moved = false;
+    const int top = ns ? *std::max_element(cnt.begin(), cnt.end()) : 0;
+    for (int s0 = 0; s0 < ns && !moved; ++s0) {
+      if (cnt[s0] != top) continue;
+      std::vector<int> via(ns, -1), queue(1, s0);  // via[s]: the pair over which the search reached s
+      std::vector<char> seen(ns, 0);
+      seen[s0] = 1;
+      for (size_t h = 0; h < queue.size() && !moved; ++h) {
+        const int u = queue[h];
+        for (int p : inc[u]) {
+          if (owner[p] != u) continue;
+          const int v = sa(p) == u ? sb(p) : sa(p);
+          if (seen[v]) continue;
+          seen[v] = 1;
+          via[v] = p;
+          if (cnt[v] <= top - 2) {
+            for (int w = v; w != s0;) {  // hand every pair of the path to its far end
+              const int q = via[w], prev = sa(q) == w ? sb(q) : sa(q);
+              owner[q] = w;
+              w = prev;
+            }
+            cnt[s0]--;
+            cnt[v]++;
+            moved = true;
+            break;
+          }
+          queue.push_back(v);
+        }
+      }
+    }
+  }
+  const int rounds = ns ? *std::max_element(cnt.begin(), cnt.end()) : 0;
+  if (rounds > MAX_SROUNDS) return;
+  for (int l = 0; l < SR_LANES; ++l)
+    for (int r = 0; r < MAX_SROUNDS; ++r) d.sr_partner[l][r] = (uint8_t)l;
+  std::vector<int> fill(ns, 0);
+  for (int p = 0; p < np; ++p) {
+    const int s = owner[p], r = fill[s]++;
+    d.sr_partner[s][r] = (uint8_t)(sa(p) == s ? sb(p) : sa(p));
+  }
+  d.sr_rounds = rounds;
+  d.sr_ok = 1;
 }
 
 // ------------------------------------------------------------------------------------------ scene

@@ -13,6 +13,8 @@ constexpr int MAX_BODY = 8;     // moving bodies (6)
 constexpr int MAX_SPAIRS = 768; // sphere pairs of the enabled link pairs (499)
 constexpr int MAX_PRIM = 8;     // exact box / cylinder primitives (6: the URDF's box and cylinder links)
 constexpr int MAX_PPAIRS = 320; // (primitive, sphere) pairs of the enabled link pairs (187)
+constexpr int SR_LANES = 64;    // self test in rounds: one item (sphere or primitive) per lane of a wavefront
+constexpr int MAX_SROUNDS = 16; // and at most this many sphere pairs owned by one sphere (10 for robotino)
 constexpr int NJ = 8;           // planning joints
 constexpr int BLOCK = 512;      // threads per workgroup (8 wavefronts, 2 per SIMD)
 
@@ -47,7 +49,19 @@ struct RobotDev {
   double sp_rr2[MAX_SPAIRS];
   double q_min[NJ], q_max[NJ];
   int rev[NJ];
+  // the self test in rounds (collide_wide; finish_pairs, self_rounds): lane s owns sphere s, every sphere pair belongs
+  // to one of its two spheres, and a sphere's pairs are its rounds 0, 1, ... -- sr_partner[s][r] is the other sphere of
+  // the pair sphere s owns in round r; an empty slot holds s itself (no sphere is paired with itself).  The pair's
+  // threshold is formed where it is used, (r_s + r_partner)^2 rounded as sp_rr2 is: the sum commutes, so these are
+  // sp_rr2's bits, and a table of them ([MAX_SROUNDS][SR_LANES] doubles, 8 KB) would not fit beside plan_kernel's LDS.
+  // sr_ok: the model qualifies (one item per lane, sr_rounds within MAX_SROUNDS); else the table is empty and the flat
+  // lists above are what every kernel reads.  sph_pmask[s]: bit p set iff (primitive p, sphere s) is in pp_ps;
+  // prim_cyl: bit p set iff primitive p is a cylinder.
+  int sr_ok, sr_rounds, prim_cyl, sr_pad;
+  alignas(16) uint8_t sr_partner[SR_LANES][MAX_SROUNDS];
+  uint8_t sph_pmask[MAX_SPH];
 };
+static_assert(MAX_PRIM <= 8, "a sphere's primitives in one byte");
 
 
 // Occupancy grid of one scene (device pointers).  Cell (i,j,k) is the box [o + i*res, o + (i+1)*res] per
