@@ -373,17 +373,21 @@ __device__ __forceinline__ int sweep_occupied(const SceneDev& sc, const double* 
 // wave_sphere_map).  A candidate that does not fit (more than 64 bricks, or the buffer full) is swept by
 // wave_sphere_map itself.  The outcome (any candidate touching an occupied cell) is the same as sweeping them one
 // after the other; wave_sphere_map pays one load round trip per candidate.
+// It comes in two halves, for a caller with work to do while the words are on their way (collide_wide):
+// map_staged_issue assigns the slots and issues the loads into registers (v: this lane's words, slots u * 64 + lane;
+// spill: the candidates of group 0 / 1, a bit per lane, that wave_sphere_map sweeps; base: slots in use),
+// map_staged_sweep stores them and sweeps.  wave_map_staged is one after the other.
 template <int CAP = MAP_STAGE_W, typename OffT = uint8_t>
-__device__ __forceinline__ bool wave_map_staged(const RobotDev* __restrict__ rb, const SceneDev& sc, const double (*wc)[3],
-                                                const uint32_t* cand, int nsph, uint64_t* buf, uint8_t* owner,
-                                                OffT* off, int lane, uint16_t* list = nullptr) {
+__device__ __forceinline__ void map_staged_issue(const RobotDev* __restrict__ rb, const SceneDev& sc, const double (*wc)[3],
+                                                 const uint32_t* cand, int nsph, uint8_t* owner, OffT* off, int lane,
+                                                 uint64_t (&v)[(CAP + 63) / 64], uint64_t (&spill)[2], int& base_out) {
   constexpr OffT NONE = (OffT)~(OffT)0;
   static_assert(CAP < (int)NONE, "slot offsets");
   // slots: sphere s = g * 64 + lane of group g.  Staged are the candidates (of at most 64 bricks) whose inclusive
   // prefix of brick counts still ends within the buffer: a prefix of them in sphere order, so the words [0, base)
   // all have an owner; off[s] = first slot of a staged candidate, else 255
   int base = 0;
-  uint64_t spill[2] = {0, 0};  // candidates of group 0 / 1 (bit per lane) swept by wave_sphere_map
+  spill[0] = spill[1] = 0;
   for (int g = 0; g < 2 && g * 64 < nsph; ++g) {
     const int s = g * 64 + lane;
     const bool is_c = s < nsph && ((cand[s >> 5] >> (s & 31)) & 1u);
@@ -404,9 +408,8 @@ __device__ __forceinline__ bool wave_map_staged(const RobotDev* __restrict__ rb,
     if (sm) base += __builtin_amdgcn_readlane(inc, 63 - __builtin_clzll(sm));
   }
   wave_sync();
-  // one round: every staged word loaded (two slots per lane), then stored
+  // one round: every staged word loaded (slots u * 64 + lane), then stored
   constexpr int SU = (CAP + 63) / 64;
-  uint64_t v[SU];
 #pragma unroll
   for (int u = 0; u < SU; ++u) {
     v[u] = 0;
@@ -420,6 +423,15 @@ __device__ __forceinline__ bool wave_map_staged(const RobotDev* __restrict__ rb,
       v[u] = sc.bricks[((size_t)(b0[2] + bk) * sc.bny + (b0[1] + bj)) * sc.bnx + (b0[0] + bi)];
     }
   }
+  base_out = base;
+}
+template <int CAP = MAP_STAGE_W, typename OffT = uint8_t>
+__device__ __forceinline__ bool map_staged_sweep(const RobotDev* __restrict__ rb, const SceneDev& sc, const double (*wc)[3],
+                                                 const uint32_t* cand, int nsph, uint64_t* buf, const OffT* off, int lane,
+                                                 uint16_t* list, const uint64_t (&v)[(CAP + 63) / 64],
+                                                 const uint64_t (&spill)[2], int base) {
+  constexpr OffT NONE = (OffT)~(OffT)0;
+  constexpr int SU = (CAP + 63) / 64;
 #pragma unroll
   for (int u = 0; u < SU; ++u)
     if (u * 64 + lane < base) buf[u * 64 + lane] = v[u];
@@ -492,6 +504,15 @@ __device__ __forceinline__ bool wave_map_staged(const RobotDev* __restrict__ rb,
     }
   }
   return false;
+}
+template <int CAP = MAP_STAGE_W, typename OffT = uint8_t>
+__device__ __forceinline__ bool wave_map_staged(const RobotDev* __restrict__ rb, const SceneDev& sc, const double (*wc)[3],
+                                                const uint32_t* cand, int nsph, uint64_t* buf, uint8_t* owner,
+                                                OffT* off, int lane, uint16_t* list = nullptr) {
+  uint64_t v[(CAP + 63) / 64], spill[2];
+  int base;
+  map_staged_issue<CAP, OffT>(rb, sc, wc, cand, nsph, owner, off, lane, v, spill, base);
+  return map_staged_sweep<CAP, OffT>(rb, sc, wc, cand, nsph, buf, off, lane, list, v, spill, base);
 }
 
 // ---------------------------------------------------------------------------------------------- exact primitives
@@ -592,53 +613,79 @@ __device__ __forceinline__ int prim_box_relation(int ty, const double* __restric
 // inside the primitive is a hit, a separated brick is skipped, and the undecided bricks are swept one after the other
 // with a lane per cell (prim_cell, ballot early exit).  The outcome is the exhaustive per-cell test's; a lane no longer
 // walks its brick's occupied cells serially (up to 64 dependent prim_cell tests next to a solid obstacle).
-__device__ __forceinline__ bool wave_prim_map(const SceneDev& sc, int ty, const double* __restrict__ h, const double* pw,
-                                              int lane) {
-  int lo[3], hi[3];
-  if (!prim_reach(ty, h, pw, sc, lo, hi)) return false;
-  const int bi0 = lo[0] >> 2, bj0 = lo[1] >> 2, bk0 = lo[2] >> 2;
-  const int nbi = (hi[0] >> 2) - bi0 + 1, nbj = (hi[1] >> 2) - bj0 + 1, nbk = (hi[2] >> 2) - bk0 + 1;
-  const int nb = nbi * nbj * nbk;
-  for (int b0 = 0; b0 < nb; b0 += 64) {
-    const int b = b0 + lane;
-    uint64_t w = 0;
-    int bi = 0, bj = 0, bk = 0, rel = 0;
-    if (b < nb) {
-      bi = bi0 + b % nbi;
-      const int t = b / nbi;
-      bj = bj0 + t % nbj;
-      bk = bk0 + t / nbj;
-      w = sc.bricks[((size_t)bk * sc.bny + bj) * sc.bnx + bi];
-      if (w) {
-        const int il = max(lo[0] - 4 * bi, 0), ih = min(hi[0] - 4 * bi, 3);
-        const int jl = max(lo[1] - 4 * bj, 0), jh = min(hi[1] - 4 * bj, 3);
-        const int kl = max(lo[2] - 4 * bk, 0), kh = min(hi[2] - 4 * bk, 3);
-        const uint32_t xm = ((2u << ih) - 1u) & ~((1u << il) - 1u);
-        uint32_t row = 0;
-        for (int jj = jl; jj <= jh; ++jj) row |= xm << (4 * jj);
-        uint64_t m = 0;
-        for (int kk = kl; kk <= kh; ++kk) m |= (uint64_t)row << (16 * kk);
-        w &= m;
-        if (w)
-          rel = prim_box_relation(ty, h, pw, sc.ox + (double)(4 * bi + il) * sc.res, sc.ox + (double)(4 * bi + ih + 1) * sc.res,
-                                  sc.oy + (double)(4 * bj + jl) * sc.res, sc.oy + (double)(4 * bj + jh + 1) * sc.res,
-                                  sc.oz + (double)(4 * bk + kl) * sc.res, sc.oz + (double)(4 * bk + kh + 1) * sc.res);
-      }
-    }
-    if (__ballot(rel == 2)) return true;
-    // the undecided bricks, a lane per cell
-    for (uint64_t um = __ballot(rel == 1); um;) {
-      const int src = __builtin_ctzll(um);  // (wave-uniform: the brick's words and indices by v_readlane)
-      um &= um - 1;
-      const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w, src);
-      const uint32_t whi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w >> 32), src);
-      const int sbi = __builtin_amdgcn_readlane(bi, src), sbj = __builtin_amdgcn_readlane(bj, src);
-      const int sbk = __builtin_amdgcn_readlane(bk, src);
-      const bool set = ((lane < 32 ? wlo >> lane : whi >> (lane - 32)) & 1u) != 0;
-      const bool hit = set && prim_cell(ty, h, pw, sc, 4 * sbi + (lane & 3), 4 * sbj + ((lane >> 2) & 3), 4 * sbk + (lane >> 4));
-      if (__ballot(hit)) return true;
+// It comes in two halves, for a caller with work to do while the words are on their way (collide_wide): prim_bricks
+// gives the reach, prim_brick_word loads a brick's word, prim_sweep_bricks classifies and sweeps 64 bricks whose words
+// the lanes hold.  wave_prim_map is one after the other, 64 bricks at a time.
+struct PrimBricks {
+  int lo[3], hi[3];        // the reach in cells
+  int bi0, bj0, bk0;       // its first brick
+  int nbi, nbj, nb;        // brick counts along x and y, and in all (0: no reach)
+};
+__device__ __forceinline__ bool prim_bricks(const SceneDev& sc, int ty, const double* __restrict__ h, const double* pw,
+                                            PrimBricks& R) {
+  R.nb = 0;
+  if (!prim_reach(ty, h, pw, sc, R.lo, R.hi)) return false;
+  R.bi0 = R.lo[0] >> 2; R.bj0 = R.lo[1] >> 2; R.bk0 = R.lo[2] >> 2;
+  R.nbi = (R.hi[0] >> 2) - R.bi0 + 1; R.nbj = (R.hi[1] >> 2) - R.bj0 + 1;
+  R.nb = R.nbi * R.nbj * ((R.hi[2] >> 2) - R.bk0 + 1);
+  return true;
+}
+// Occupancy word of brick b of the reach (0 past its end).
+__device__ __forceinline__ uint64_t prim_brick_word(const SceneDev& sc, const PrimBricks& R, int b) {
+  if (b >= R.nb) return 0;
+  const int bi = R.bi0 + b % R.nbi, t = b / R.nbi;
+  const int bj = R.bj0 + t % R.nbj, bk = R.bk0 + t / R.nbj;
+  return sc.bricks[((size_t)bk * sc.bny + bj) * sc.bnx + bi];
+}
+// Bricks b0 .. b0 + 63 of the reach, the lane holding brick b0 + lane's word w.
+__device__ __forceinline__ bool prim_sweep_bricks(const SceneDev& sc, int ty, const double* __restrict__ h,
+                                                  const double* pw, const PrimBricks& R, int b0, uint64_t w, int lane) {
+  const int* lo = R.lo;
+  const int* hi = R.hi;
+  const int b = b0 + lane;
+  int bi = 0, bj = 0, bk = 0, rel = 0;
+  if (b < R.nb) {
+    bi = R.bi0 + b % R.nbi;
+    const int t = b / R.nbi;
+    bj = R.bj0 + t % R.nbj;
+    bk = R.bk0 + t / R.nbj;
+    if (w) {
+      const int il = max(lo[0] - 4 * bi, 0), ih = min(hi[0] - 4 * bi, 3);
+      const int jl = max(lo[1] - 4 * bj, 0), jh = min(hi[1] - 4 * bj, 3);
+      const int kl = max(lo[2] - 4 * bk, 0), kh = min(hi[2] - 4 * bk, 3);
+      const uint32_t xm = ((2u << ih) - 1u) & ~((1u << il) - 1u);
+      uint32_t row = 0;
+      for (int jj = jl; jj <= jh; ++jj) row |= xm << (4 * jj);
+      uint64_t m = 0;
+      for (int kk = kl; kk <= kh; ++kk) m |= (uint64_t)row << (16 * kk);
+      w &= m;
+      if (w)
+        rel = prim_box_relation(ty, h, pw, sc.ox + (double)(4 * bi + il) * sc.res, sc.ox + (double)(4 * bi + ih + 1) * sc.res,
+                                sc.oy + (double)(4 * bj + jl) * sc.res, sc.oy + (double)(4 * bj + jh + 1) * sc.res,
+                                sc.oz + (double)(4 * bk + kl) * sc.res, sc.oz + (double)(4 * bk + kh + 1) * sc.res);
     }
   }
+  if (__ballot(rel == 2)) return true;
+  // the undecided bricks, a lane per cell
+  for (uint64_t um = __ballot(rel == 1); um;) {
+    const int src = __builtin_ctzll(um);  // (wave-uniform: the brick's words and indices by v_readlane)
+    um &= um - 1;
+    const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w, src);
+    const uint32_t whi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w >> 32), src);
+    const int sbi = __builtin_amdgcn_readlane(bi, src), sbj = __builtin_amdgcn_readlane(bj, src);
+    const int sbk = __builtin_amdgcn_readlane(bk, src);
+    const bool set = ((lane < 32 ? wlo >> lane : whi >> (lane - 32)) & 1u) != 0;
+    const bool hit = set && prim_cell(ty, h, pw, sc, 4 * sbi + (lane & 3), 4 * sbj + ((lane >> 2) & 3), 4 * sbk + (lane >> 4));
+    if (__ballot(hit)) return true;
+  }
+  return false;
+}
+__device__ __forceinline__ bool wave_prim_map(const SceneDev& sc, int ty, const double* __restrict__ h, const double* pw,
+                                              int lane) {
+  PrimBricks R;
+  if (!prim_bricks(sc, ty, h, pw, R)) return false;
+  for (int b0 = 0; b0 < R.nb; b0 += 64)
+    if (prim_sweep_bricks(sc, ty, h, pw, R, b0, prim_brick_word(sc, R, b0 + lane), lane)) return true;
   return false;
 }
 
@@ -949,6 +996,8 @@ struct WideLds {
   WideWave w[NWAVE];
   int coll[NWAVE];                          // configuration c: 1 = in collision
 };
+// (plan_kernel's LDS ends 5 264 B below the 160 KB of a workgroup: the job tile's share stays what it is)
+static_assert(sizeof(WideLds) <= 51744 + 5264, "WideLds has outgrown plan_kernel's LDS headroom");
 
 // What a lane of collide_wide needs of the robot model, the map configuration and the scene, and what never changes
 // during a launch: read once per workgroup (wide_const) and kept in registers over all the tiles it runs.  A lane always
@@ -1072,7 +1121,10 @@ __device__ __forceinline__ WideConst wide_const_load(const WideStash& S, const S
 // isInCollision is map || self, collision_checker.hpp:104-121), so the split changes no result; a wavefront stops
 // after its first hit or once another wavefront of the group reported one.  The caller zeroes L.coll[0 .. ct) before
 // the barrier that publishes q_lds; on return (after a block barrier) L.coll[c] is 1 for the colliding configurations.
-// prof (thread 0): stage clocks A, B, centres + prefilter loads, whole tile, as collide_tile's.
+// prof (thread 0): stage clocks A, B, centres + prefilter loads, whole tile, as collide_tile's.  prof2 (thread 0, 8
+// entries): wave 0's split of the last stage -- the prefilter loads from issue to arrival; the primitives' brick words
+// from issue to arrival; primitive sweeps; the staged spheres' slots and brick words up to their arrival; sphere
+// sweeps; self test; the tile's end after wave 0's; and the work in between (candidates read, reaches).
 __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, const WideConst& K, int ct, int nc,
                                              const double (*q_lds)[NJ], int self, int map, WideLds& L,
                                              const TileOrder* ord = nullptr,
@@ -1083,7 +1135,7 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
   const int c = wave / G, g = wave - c * G;
   WideWave& W = L.w[wave];
   const unsigned long long t0 = (prof && threadIdx.x == 0) ? wall_clock64() : 0;
-  unsigned long long ta = t0, tb = t0, tc = t0;
+  unsigned long long ta = t0, tb = t0, tc = t0, tw0 = 0;
   int live = c < nc;
   if (live && ord) live = !(ord->ord[c] > ord->first(ord->grp[c]));
   if (__builtin_amdgcn_readfirstlane(live)) {
@@ -1231,12 +1283,29 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
         }
       }
     }
+    // wave 0's clocks of the rest (prof2, thread 0): clk() now; arrived() once every load issued so far has come back.
+    // (The fields are read with flat loads, which count on the LDS counter too: a clock read waits for them, so a wait
+    // is clocked from before the loads' issue.)
+    const bool pf2 = prof2 && threadIdx.x == 0;
+    auto clk = [&]() __attribute__((always_inline)) { return pf2 ? wall_clock64() : 0ull; };
+    auto arrived = [&]() __attribute__((always_inline)) {
+      if (pf2) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      return clk();
+    };
+    unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq = clk(), tn;
+    auto lap = [&](int i, bool wait = false) __attribute__((always_inline)) {
+      tn = wait ? arrived() : clk();
+      pc[i] += tn - tq;
+      tq = tn;
+    };
+    enum { PC_PRE = 0, PC_PWAIT = 1, PC_PSWEEP = 2, PC_SWAIT = 3, PC_SSWEEP = 4, PC_SELF = 5, PC_TAIL = 6, PC_BETWEEN = 7 };
     uint32_t dv[2], sv[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       dv[u] = cell[u] < 0 ? 0xffffffffu : (sc.d2b ? (uint32_t)sc.d2b[cell[u]] : (uint32_t)sc.d2[cell[u]]);
       sv[u] = pcell[u] < 0 ? 0xffffffffu : (uint32_t)K.slab[pcell[u]];
     }
+    lap(PC_PRE, true);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int it = u * 64 + lane;
@@ -1245,36 +1314,18 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
     }
     wave_sync();
     if (prof && threadIdx.x == 0) tc = wall_clock64();
-    // map: this wavefront's candidate primitives, then its candidate spheres (their brick words in one round trip).
+    const bool rounds = (K.sr & 1) && G < NWAVE;
     // Another wavefront of the group may have reported a hit meanwhile (G > 1 only: with one wavefront per
     // configuration nobody else writes L.coll[c]).
-    bool hit = false;
-    unsigned long long tp0 = (prof2 && threadIdx.x == 0) ? wall_clock64() : 0, tp1 = tp0, tp2 = tp0;
-    for (uint32_t pm = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.pcand); pm && !hit;) {
-      const int p = __builtin_ctz(pm);
-      pm &= pm - 1;
-      if (G > 1 &&
-          __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))
-        break;
-      const double pw[5] = {W.u.c.pw[p][0], W.u.c.pw[p][1], W.u.c.pw[p][2], W.u.c.pw[p][3], W.u.c.pw[p][4]};
-      hit = wave_prim_map(sc, rb->prim_type[p], &rb->prim_h[p * 3], pw, lane);
-    }
-    if (prof2 && threadIdx.x == 0) tp1 = wall_clock64();
-    uint32_t any = 0;
-    for (int wd = 0; wd < (MAX_SPH + 31) / 32; ++wd) any |= W.cand[wd];
-    if (!hit && __builtin_amdgcn_readfirstlane((int)(any != 0)) &&
-        !(G > 1 &&
-          __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))))
-      hit = wave_map_staged<WIDE_STAGE_W, uint16_t>(rb, sc, W.u.c.wc, W.cand, nsph, W.stage, W.owner, W.off, lane,
-                                                    W.list);
-    if (prof2 && threadIdx.x == 0) tp2 = wall_clock64();
-    // self: this wavefront's share of the sphere pairs, then of the (primitive, sphere) pairs -- in rounds for a model
-    // with one item per lane, else in 64-pair chunks of the flat lists
-    if (self && !hit &&
-        !(G > 1 &&
-          __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)))) {
+    auto group_hit = [&]() __attribute__((always_inline)) {
+      return G > 1 &&
+             __builtin_amdgcn_readfirstlane(__hip_atomic_load(&L.coll[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    };
+    // self: this wavefront's share of the sphere pairs, then of the (primitive, sphere) pairs -- in
+    // rounds for a model with one item per lane, else in 64-pair chunks of the flat lists
+    auto self_rounds = [&]() __attribute__((always_inline)) {
       bool sh = false;
-      if ((K.sr & 1) && G < NWAVE) {
+      {
         // in rounds (RobotDev::sr_*; the counts and the primitives' types are bits of the scalar K.sr, so nothing is
         // waited for before the first loads): the lane owns sphere `lane` -- its centre, radius, primitive mask and
         // row of partners come in one batch at addresses known from the lane number, with the first primitives' half
@@ -1344,7 +1395,12 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
             if (p0 < npr) prim_loads();
           }
         }
-      } else {
+      }
+      return sh;
+    };
+    auto self_flat = [&]() __attribute__((always_inline)) {
+      bool sh = false;
+      {
         // the flat lists (a model with more than one item per lane or more rounds than the table holds, SMP_SELF_FLAT,
         // G = 8)
         const int nsp = rb->n_spairs, npp = rb->n_ppairs, ks = (nsp + 63) >> 6;
@@ -1369,11 +1425,48 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
           }
         }
       }
-      hit = __ballot(sh) != 0;
+      return sh;
+    };
+    // map: this wavefront's candidate primitives, then its candidate spheres (their brick words in one round trip);
+    // wave_prim_map and wave_map_staged, spelt out in their halves for the clocks
+    bool hit = false;
+    uint32_t pm = (uint32_t)__builtin_amdgcn_readfirstlane((int)W.pcand);
+    lap(PC_BETWEEN);
+    while (pm && !hit) {
+      const int p = __builtin_ctz(pm);
+      pm &= pm - 1;
+      if (group_hit()) break;
+      const double pw[5] = {W.u.c.pw[p][0], W.u.c.pw[p][1], W.u.c.pw[p][2], W.u.c.pw[p][3], W.u.c.pw[p][4]};
+      PrimBricks R;
+      if (!prim_bricks(sc, rb->prim_type[p], &rb->prim_h[p * 3], pw, R)) continue;
+      for (int b0 = 0; !hit && b0 < R.nb; b0 += 64) {
+        lap(PC_BETWEEN);
+        const uint64_t w = prim_brick_word(sc, R, b0 + lane);
+        lap(PC_PWAIT, true);
+        hit = prim_sweep_bricks(sc, rb->prim_type[p], &rb->prim_h[p * 3], pw, R, b0, w, lane);
+        lap(PC_PSWEEP);
+      }
     }
-    if (prof2 && threadIdx.x == 0) {  // wave 0: primitive sweeps, sphere sweeps, self test
-      const unsigned long long tp3 = wall_clock64();
-      prof2[0] += tp1 - tp0; prof2[1] += tp2 - tp1; prof2[2] += tp3 - tp2;
+    uint32_t any = 0;
+    for (int wd = 0; wd < (MAX_SPH + 31) / 32; ++wd) any |= W.cand[wd];
+    if (!hit && __builtin_amdgcn_readfirstlane((int)(any != 0)) && !group_hit()) {
+      uint64_t sv64[(WIDE_STAGE_W + 63) / 64], spill[2];
+      int sbase;
+      lap(PC_BETWEEN);
+      map_staged_issue<WIDE_STAGE_W, uint16_t>(rb, sc, W.u.c.wc, W.cand, nsph, W.owner, W.off, lane, sv64, spill, sbase);
+      lap(PC_SWAIT, true);
+      hit = map_staged_sweep<WIDE_STAGE_W, uint16_t>(rb, sc, W.u.c.wc, W.cand, nsph, W.stage, W.off, lane, W.list, sv64,
+                                                     spill, sbase);
+      lap(PC_SSWEEP);
+    }
+    lap(PC_BETWEEN);
+    if (self && !hit && !group_hit()) {
+      hit = __ballot(rounds ? self_rounds() : self_flat()) != 0;
+      lap(PC_SELF);
+    }
+    if (pf2) {  // wave 0's split of the stage
+      for (int i = 0; i < 8; ++i) prof2[i] += pc[i];
+      tw0 = wall_clock64();
     }
     if (hit && lane == 0) {
       atomicOr(&L.coll[c], 1);
@@ -1384,6 +1477,7 @@ __device__ __forceinline__ void collide_wide(const RobotDev* __restrict__ rb, co
   if (prof && threadIdx.x == 0) {
     prof[0] += ta - t0; prof[1] += tb - ta; prof[2] += tc - tb; prof[3] += wall_clock64() - tb;
   }
+  if (prof2 && threadIdx.x == 0 && tw0) prof2[6] += wall_clock64() - tw0;  // the tile's end after wave 0's
 }
 
 }  // namespace smp

@@ -66,7 +66,7 @@ for name in os.environ.get("SMP_SETS", "tree-edges,expand-edges,connect-edges,ra
     for tile, grid in shapes:
         ms = ctypes.c_double()
         hz = ctypes.c_double()
-        ticks = (ctypes.c_uint64 * 12)()
+        ticks = (ctypes.c_uint64 * 16)()
         L.check(lib.smp_probe_check_latency(gp.h, soa.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, 1, 1, grid, tile,
                                             ctypes.byref(ms), ticks, ctypes.byref(hz)))
         ct = abs(tile)
@@ -75,9 +75,25 @@ for name in os.environ.get("SMP_SETS", "tree-edges,expand-edges,connect-edges,ra
         print("%-10s tile %2d n %7d grid %5d: %.2f ms  %.3g configs/s  per tile %.2f us  stages(us) A %.2f B %.2f C0 %.2f C %.2f"
               % (name, tile, n, grid, ms.value, n / (ms.value * 1e-3), ms.value * 1e3 / tiles * (grid if grid > 1 else 1) /
                  (1 if grid == 1 else min(grid, tiles)), *per_tile_us[:4]), flush=True)
+        if tile < 0 and grid == 1:
+            # the same tiles with no clock in the kernel (smp_probe_check_shape; host clock around copy in, kernel, copy
+            # out and synchronise, best of three): the figure to compare builds by, as the stage clocks above cost
+            # wave 0 time of their own, and more of it the finer they split
+            import time
+            valid = np.zeros(n, np.uint8)
+            best = math.inf
+            for _ in range(3):
+                t0 = time.perf_counter()
+                L.check(lib.smp_probe_check_shape(gp.h, soa.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n, 1, 1, tile,
+                                                  1, valid.ctypes.data_as(ctypes.c_void_p)))
+                best = min(best, time.perf_counter() - t0)
+            print("   without clocks: %.2f ms, per tile %.2f us" % (best * 1e3, best * 1e6 / tiles), flush=True)
         if tile > 0:
             print("   shader clock %.3f GHz; wave 0 in C: centres + map sweeps %.2f us, self test %.2f us per tile" % (
                 ticks[4] / (ticks[5] / hz.value) / 1e9 if ticks[5] else 0, per_tile_us[6], per_tile_us[7]), flush=True)
         else:
-            print("   shader clock %.3f GHz; wave 0: primitive sweeps %.2f us, sphere sweeps %.2f us, self %.2f us per "
-                  "tile" % (ticks[4] / (ticks[5] / hz.value) / 1e9 if ticks[5] else 0, *per_tile_us[6:9]), flush=True)
+            # (a wait runs from the loads' issue to their arrival)
+            print("   shader clock %.3f GHz; wave 0 (us per tile): prefilter loads %.2f, primitive brick loads %.2f sweeps "
+                  "%.2f, sphere slots and brick loads %.2f sweeps %.2f, self %.2f, in between %.2f; tile ends %.2f after "
+                  "wave 0" % (ticks[4] / (ticks[5] / hz.value) / 1e9 if ticks[5] else 0, *per_tile_us[6:12],
+                              per_tile_us[13], per_tile_us[12]), flush=True)
