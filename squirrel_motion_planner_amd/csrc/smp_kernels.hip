@@ -444,6 +444,11 @@ struct PlanLds {
   unsigned rw_at0;              // leader: rewire commits of tree_A at the start of the iteration (records must match)
   int n_at0;                    // leader: nodes of tree_A at the start of the iteration (early asks' snapshot)
   int sc_t, sc_rerun;           // scout: the pass's tree; 1 = the tree was rewired under the pass (rebuild it)
+  int sc_stale_f;               // scout: the leader has passed the pass's iteration, as last read under a job (sc_early_send)
+  // scout: the rows of the near set's hi list (rewire's candidates: configuration, cost[0], parent), by position in
+  // hi_i, loaded in the round trip of choose's candidate rows (near_set<20>: at most 20 entries)
+  double sc_hq[MAXE][NJ], sc_hc[MAXE];
+  int sc_hp[MAXE];
   int rb_go[2];                 // scout: decision words of the rebuild wait (double-buffered like sp_go)
   long long sc_k;               // scout: the pass's iteration
   int eg_hit[MAXE];
@@ -2430,50 +2435,120 @@ __device__ __forceinline__ bool take_spec(int ov) {
   return hit;
 }
 
+// Scout, post-solution pass: the words of a record stage that are final before the stage's collision job, sent from
+// the edge batch while the helpers check the job's tiles (edge_validity's window; where no job runs, in its place).
+// `early` names the stage (EARLY_*, block-uniform; EARLY_NONE: nothing -- every leader call), `epar` the record slot.
+// A ScoutEdge's last word {first, pad} is the job's result and is left to sc_first_send: an early store never touches
+// a word that a later store of the same stage writes (two stores to one address from different waves have no order
+// before the drain).  `read_stale` (the paths without a job): thread 0 also reads whether the leader has passed the
+// pass's iteration (what sc_stale reads) into g_L.sc_stale_f; under a job every round of the collection poll sets it (at
+// least one round runs), so the window does not wait for that load and no dependent load follows the job's result.
+enum { EARLY_NONE = 0, EARLY_EXPAND = 1, EARLY_CHOOSE = 2, EARLY_REWIRE = 3 };
+constexpr int EDGE_EARLY_W = (int)(offsetof(ScoutEdge, first) / 8);  // 8-byte words of a ScoutEdge before {first, pad}
+static_assert(EDGE_EARLY_W == 2 * NJ + 3, "ScoutEdge: s, g, acc, then {first, pad}");
+__device__ __forceinline__ int sc_stale_now(const ScoutBoard* sb) {  // (one lane; advisory: a stale pass only saves work)
+  return (long long)ld_agent(&sb->cur) > g_L.sc_k || ld_agent(&sb->stop);
+}
+__device__ __forceinline__ void sc_early_send(const Ctx& C, int early, int epar, int E, bool read_stale) {
+  if (early == EARLY_NONE) return;
+  ScoutBoard* sb = C.Q.scb;
+  ScoutRec* rec = &sb->rec[epar];
+  if (read_stale && threadIdx.x == 0) g_L.sc_stale_f = sc_stale_now(sb);
+  const int g0 = early == EARLY_EXPAND ? 0 : early == EARLY_CHOOSE ? SCOUT_CHOOSE0 : SCOUT_REWIRE0;
+  for (int i = threadIdx.x; i < E * EDGE_EARLY_W; i += BLOCK) {
+    const int e = i / EDGE_EARLY_W, k = i - e * EDGE_EARLY_W;
+    const double v = k < NJ ? g_L.eg_start[e][k] : k < 2 * NJ ? g_L.eg_target[e][k - NJ] : g_L.eg_acc[e][k - 2 * NJ];
+    st_agent(reinterpret_cast<unsigned long long*>(&rec->e[g0 + e]) + k, (unsigned long long)__double_as_longlong(v));
+  }
+  if (early == EARLY_EXPAND) {
+    // R.ex of edge 0: ext, step, end, acc from the batch, {ok, pad} from the LDS record (set before the job)
+    constexpr int XW = (int)(sizeof(ScoutExpand) / 8);
+    static_assert(XW == 3 * NJ + 3 + 1 && offsetof(ScoutExpand, ok) == (XW - 1) * 8, "ScoutExpand: ext, step, end, acc, {ok, pad}");
+    const int k = (int)threadIdx.x - 64;  // (wave 1: wave 0 has the edge's words)
+    if (k >= 0 && k < XW) {
+      unsigned long long w;
+      if (k == XW - 1) w = *reinterpret_cast<const unsigned long long*>(&g_L.sr.ex.ok);
+      else w = (unsigned long long)__double_as_longlong(k < NJ ? g_L.eg_target[0][k] : k < 2 * NJ ? g_L.eg_step[0][k - NJ] :
+                                                        k < 3 * NJ ? g_L.eg_end[0][k - 2 * NJ] : g_L.eg_acc[0][k - 3 * NJ]);
+      st_agent(reinterpret_cast<unsigned long long*>(&rec->ex) + k, w);
+    }
+  } else {
+    // the counts (n_choose, n_rewire, pad[2]: set in the LDS record before the job)
+    const int k = (int)threadIdx.x - (BLOCK - 64);  // (the last wave: the lowest waves have the edges' words)
+    if (k >= 0 && k < 2) st_agent(reinterpret_cast<unsigned long long*>(&rec->n_choose) + k,
+                                  reinterpret_cast<const unsigned long long*>(&g_L.sr.n_choose)[k]);
+  }
+}
+// Scout, after the stage's job: the {first, pad} words of the stage's E record edges (-1 = not checked).
+__device__ __forceinline__ void sc_first_send(const Ctx& C, int early, int epar, int E) {
+  const int g0 = early == EARLY_EXPAND ? 0 : early == EARLY_CHOOSE ? SCOUT_CHOOSE0 : SCOUT_REWIRE0;
+  if ((int)threadIdx.x < E) {
+    const int e = threadIdx.x;
+    const int first = g_L.eg_need[e] ? g_L.eg_first[e] : -1;
+    st_agent(reinterpret_cast<unsigned long long*>(&C.Q.scb->rec[epar].e[g0 + e]) + EDGE_EARLY_W,
+             (unsigned long long)(unsigned)first);
+  }
+}
+
+// The job's header (wave 0, lane e = batch edge e; `need`: the edge goes into the job, at least one does): the job edges'
+// map and the shape of the job.  edge_validity runs it in the step that decides whether a job is needed, so that one
+// barrier lies between its entry and the first payload granule.
+__device__ __forceinline__ void job_header(const Ctx& C, bool need, bool sfv) {
+  auto& J = g_L.u.job;
+  const int e = threadIdx.x;
+  const int np1 = g_L.S.n_pts + 1;
+  const int W = max(1, C.Q.nworkers);  // (a workgroup without helpers takes every tile itself)
+  const unsigned long long m = __ballot(need);
+  const int k = __popcll(m & ((1ull << e) - 1));
+  if (need) J.emap[k] = e;
+  if (e == 0) {
+    const int ne = __popcll(m);
+    J.E = ne;
+    J.np1 = np1;
+    J.nslots = ne * np1;
+    J.ct = job_tile_ct(ne * np1, W, C.Q.tile_ct);
+    J.ntiles = (ne * np1 + J.ct - 1) / J.ct;
+    J.self = g_L.S.self; J.map = g_L.S.map;
+    J.seq = ++g_L.job_seq;
+#ifdef SMP_NO_SKIP
+    J.skip = 0;
+#else
+    J.skip = J.ntiles > W;  // more tiles than workers: later rounds skip what earlier ones decided
+#endif
+    J.sfv = J.skip && sfv;
+  }
+}
 // Leader: publishes the needed edges of the batch as one job (every point of every needed edge); tile t belongs
 // to worker (t + 1) % W, so the helpers take the first W - 1 tiles and the leader only tiles W - 1, 2W - 1, ...
 // While they are checked, the leader does `ov` (overlap_work), then its own tiles, then collects the helpers'
 // tile results and reduces them to the first collision of each edge (eg_first).  A helper's tile that does not
 // arrive within 8 us of the last progress is checked by the leader itself (a duplicate result is identical, so
 // no claim is needed).
-__device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot, int ov, int ovt, bool sfv) {
+// edge_validity has run job_header and set eg_first of the batch's edges to "free", and a barrier followed.
+__device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot, int ov, int ovt, int early = 0,
+                                                  int epar = 0) {
   JobBoard* jb = C.Q.jb;
   auto& J = g_L.u.job;
   const int np1 = g_L.S.n_pts + 1;
-  const int W = max(1, C.Q.nworkers);  // (a workgroup without helpers takes every tile itself)
-  if (threadIdx.x < 64) {
-    const int e = threadIdx.x;
-    const bool need = e < E && g_L.eg_need[e] && g_L.eg_hit[e] < 0;  // edges the scout checked are not published
-    const unsigned long long m = __ballot(need);
-    const int k = __popcll(m & ((1ull << e) - 1));
-    if (need) J.emap[k] = e;
-    if (e == 0) {
-      const int ne = __popcll(m);
-      J.E = ne;
-      J.np1 = np1;
-      J.nslots = ne * np1;
-      J.ct = job_tile_ct(ne * np1, W, C.Q.tile_ct);
-      J.ntiles = (ne * np1 + J.ct - 1) / J.ct;
-      J.self = g_L.S.self; J.map = g_L.S.map;
-      J.seq = ++g_L.job_seq;
-#ifdef SMP_NO_SKIP
-      J.skip = 0;
-#else
-      J.skip = J.ntiles > W;  // more tiles than workers: later rounds skip what earlier ones decided
-#endif
-      J.sfv = J.skip && sfv;
-    }
-  }
-  if (threadIdx.x < E) g_L.eg_first[threadIdx.x] = np1;
-  __syncthreads();
+  const int W = max(1, C.Q.nworkers);
   const int ne = uni(J.E), nt = uni(J.ntiles), seq = uni(J.seq), ct = uni(J.ct);
-  if (ne == 0) {
-    // nothing to check (the scout's record had every edge): no job whose latency the scan would hide, and its
-    // result may not be needed (OV_NEAR_EXPAND when the expand edge collides) -- the caller scans if it must
-    overlap_work(C, OV_NONE, ovt);
-    return;
-  }
   const unsigned long long tj0 = threadIdx.x == 0 ? wall_clock64() : 0;
+  // payload granules (no flag and no drain: each granule carries the job number), formed straight from the batch
+  // through emap: the helpers decode the payload themselves, so nothing of J but the header fields has to be there yet
+  for (int i = threadIdx.x; i < 1 + 32 * ne; i += BLOCK) {
+    unsigned w;
+    if (i == 0) {
+      w = (unsigned)ne | (unsigned)np1 << 8 | (unsigned)(J.self != 0) << 16 | (unsigned)(J.map != 0) << 17 |
+          (unsigned)J.skip << 19 | (unsigned)J.sfv << 20 | (unsigned)__builtin_ctz((unsigned)J.ct) << 21;
+    } else {
+      const int m = i - 1, k = m >> 5, r = m & 31, j = (r & 15) >> 1, e = J.emap[k];
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(r < 16 ? g_L.eg_start[e][j] : g_L.eg_step[e][j]);
+      w = (r & 1) ? (unsigned)(bits >> 32) : (unsigned)bits;
+    }
+    st_agent(&jb->pay[i], granule(seq, w));
+  }
+  // the job's LDS fields, read by this workgroup's own and stolen tiles and by the collection: filled in the window,
+  // before the barrier below
   for (int it = threadIdx.x; it < ne * NJ; it += BLOCK) {
     const int k = it / NJ, j = it - k * NJ, e = J.emap[k];
     J.start[k][j] = g_L.eg_start[e][j];
@@ -2481,20 +2556,6 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
   }
   for (int t = threadIdx.x; t < nt; t += BLOCK) J.rdone[t] = 0;
   if (threadIdx.x < ne) J.first[threadIdx.x] = np1;
-  __syncthreads();
-  // payload granules (no flag and no drain: each granule carries the job number)
-  for (int i = threadIdx.x; i < 1 + 32 * ne; i += BLOCK) {
-    unsigned w;
-    if (i == 0) {
-      w = (unsigned)ne | (unsigned)np1 << 8 | (unsigned)(J.self != 0) << 16 | (unsigned)(J.map != 0) << 17 |
-          (unsigned)J.skip << 19 | (unsigned)J.sfv << 20 | (unsigned)__builtin_ctz((unsigned)J.ct) << 21;
-    } else {
-      const int m = i - 1, k = m >> 5, r = m & 31, j = (r & 15) >> 1;
-      const unsigned long long bits = (unsigned long long)__double_as_longlong(r < 16 ? J.start[k][j] : J.step[k][j]);
-      w = (r & 1) ? (unsigned)(bits >> 32) : (unsigned)bits;
-    }
-    st_agent(&jb->pay[i], granule(seq, w));
-  }
 #ifdef SMP_JOB_PROF
   if (threadIdx.x == 0) st_agent(&jb->dbg[0], wall_clock64());
 #endif
@@ -2502,6 +2563,7 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
   if (threadIdx.x == 0) { g_L.S.prof[P_TFK] += _pt - tj0; g_L.S.prof[P_TTEST]++; }  // job publication
   TR();
   if (threadIdx.x == 0) g_L.in_job = 1;  // the helpers are on this job's tiles: overlap scans stay local
+  sc_early_send(C, early, epar, E, false);
   __syncthreads();
   overlap_work(C, ov, ovt);
   if (threadIdx.x == 0) g_L.in_job = 0;
@@ -2525,12 +2587,17 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
   for (int k = 0;; k ^= 1) {
     if (threadIdx.x < 64) {
       int left = 0;
+      // scout: the staleness words (sc_early_send) are loaded in the same round trip as the results
+      unsigned long long cur_v = 0;
+      int stop_v = 0;
+      if (early != EARLY_NONE && threadIdx.x == 0) { cur_v = ld_agent(&C.Q.scb->cur); stop_v = ld_agent(&C.Q.scb->stop); }
       for (int t = threadIdx.x; t < nt; t += 64) {
         if (J.rdone[t]) continue;
         const unsigned long long v = ld_agent(&jb->res[t]);
         if ((int)(v >> 32) == seq) { J.rmask[t] = (unsigned)v; J.rdone[t] = 1; }
         else ++left;
       }
+      if (early != EARLY_NONE && threadIdx.x == 0) g_L.sc_stale_f = (long long)cur_v > g_L.sc_k || stop_v;
       left = __ockl_wfred_add_i32(left);  // (DPP reduction: a shuffle tree costs six LDS-latency bpermutes)
       if (threadIdx.x == 0) {
         const unsigned long long now = wall_clock64();
@@ -3526,8 +3593,10 @@ __device__ __noinline__ void local_tile(const Ctx& C, int nc) {
 // (SC_EXPAND: the expand edge, SC_CHOOSE: choose-parent candidates, SC_DONE: rewire candidates).  A needed edge
 // whose start and target equal a checked record edge bit for bit takes that edge's first collision (a pure
 // function of the two configurations) and is left out of the job.
+// `early` / `epar` (scout, post-solution pass): the record stage whose early words go out under the job
+// (sc_early_send), and the record slot; on every path they are stored, and g_L.sc_stale_f set, before the return.
 __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_first_valid, int pslot, int ov = 0, int ovt = 0,
-                              int sgrp = -1) {
+                              int sgrp = -1, int early = 0, int epar = 0) {
   const int np1 = g_L.S.n_pts + 1;
   if (threadIdx.x == 0) g_L.count_slot = pslot + 4;
   TR();
@@ -3559,7 +3628,8 @@ __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_fir
       const unsigned long long mh = __ballot(need && hit >= 0), mm = __ballot(need && hit < 0);
       if (rec && e == 0) { g_L.S.sc_edge_hit += __popcll(mh); g_L.S.sc_edge_miss += __popcll(mm); }
       // every needed edge answered by the record: no job
-      if (mm == 0 && e < E) g_L.eg_first[e] = need ? hit : np1;
+      if (e < E) g_L.eg_first[e] = mm == 0 && need ? hit : np1;
+      if (mm != 0) job_header(C, need && hit < 0, stop_first_valid);  // edges the scout checked are not published
       if (e == 0) {
         g_L.ev_job = mm != 0;
         g_L.rec_grp = -1;
@@ -3567,14 +3637,24 @@ __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_fir
       }
     }
     __syncthreads();
-    if (!uni(g_L.ev_job)) { TR(); return; }
-    edge_validity_job(C, E, pslot, ov, ovt, stop_first_valid);
-    if (threadIdx.x < E && g_L.eg_hit[threadIdx.x] >= 0) g_L.eg_first[threadIdx.x] = g_L.eg_hit[threadIdx.x];
-    __syncthreads();
+    if (!uni(g_L.ev_job)) {
+      if (early != EARLY_NONE) {  // no job to send under
+        sc_early_send(C, early, epar, E, true);
+        __syncthreads();
+      }
+      TR();
+      return;
+    }
+    edge_validity_job(C, E, pslot, ov, ovt, early, epar);
+    if (sgrp >= 0) {  // (without a record stage no edge has a record result: eg_hit is -2 throughout)
+      if (threadIdx.x < E && g_L.eg_hit[threadIdx.x] >= 0) g_L.eg_first[threadIdx.x] = g_L.eg_hit[threadIdx.x];
+      __syncthreads();
+    }
     TR();
     return;
   }
   if (threadIdx.x < E) { g_L.eg_first[threadIdx.x] = np1; g_L.eg_ptr[threadIdx.x] = 0; }
+  sc_early_send(C, early, epar, E, true);  // (no job board: under the local tiles)
   __syncthreads();
   for (;;) {
     // wave 0 (lane e = edge e): stop check, then the next tile's slots by a prefix sum of remaining points
@@ -4442,7 +4522,8 @@ __device__ void choose_parent(const Ctx& C, int t) {
 // rewireTreeInterpolation's candidates (birrt_star.cpp:5088-5096): the last min(k, max_near) near nodes, from the
 // end, whose cost exceeds x_new's -> g_L.cnt.  The hi list is in ascending (cost, id) order, so they are a suffix
 // of it; wave 0 tests them with one load each (lane l: position n_hi - 1 - l) and counts by ballot.
-__device__ void rewire_count(const TreeDev& T) {
+// (a call, as it was while the scout's pass shared it: the leader's rewire() keeps its code)
+__device__ __noinline__ void rewire_count(const TreeDev& T) {
   if (threadIdx.x < 64) {
     const int n = g_L.nk, lane = threadIdx.x;
     const int m = n >= g_L.S.max_near ? g_L.S.max_near : n;
@@ -5579,16 +5660,19 @@ __device__ void scout_iteration(const Ctx& C, long long it, int t, int X, int op
     R.pre.ok = 0;
     R.nn.ok = 0; R.ex.ok = 0; R.nr.ok = 0; R.n_choose = 0; R.n_rewire = 0; R.cc.ok = 0; R.cc.nfirst = -1;
   }
+  // the sample: the sampler's ring slot for (it, ver), if it is there within ~20 us.  The first round's loads are
+  // issued before SC_STARTED's drain, which then waits for them too: one round trip instead of two at the pass's start
+  unsigned long long v0 = 0;
+  if (threadIdx.x < 2 * NJ) v0 = ld_agent(&C.Q.sampler_jb->ring[it % SMP_RING].g[threadIdx.x]);
   if (opt) sc_publish(C, par, tag, SC_STARTED);  // (a pre-solution pass publishes its record once, at its end)
-  // the sample: the sampler's ring slot for (it, ver), if it is there within ~20 us
   if (threadIdx.x < 64) {  // wave 0 polls the slot's 16 granules (one round each time)
     const JobBoard* lb = C.Q.sampler_jb;
     const unsigned want = ring_tag(it, ver);
     const unsigned long long t0 = wall_clock64();
     int ok = 0;
-    for (;;) {
-      unsigned long long v = 0;
-      if (threadIdx.x < 2 * NJ) v = ld_agent(&lb->ring[it % SMP_RING].g[threadIdx.x]);
+    for (bool first_round = true;; first_round = false) {
+      unsigned long long v = v0;
+      if (!first_round && threadIdx.x < 2 * NJ) v = ld_agent(&lb->ring[it % SMP_RING].g[threadIdx.x]);
       const bool cur = threadIdx.x >= 2 * NJ || (unsigned)(v >> 32) == want;
       if (__ballot(!cur) == 0) {
         const unsigned hi = (unsigned)odd_lane_of_pair((int)(unsigned)v);
@@ -5665,8 +5749,10 @@ redo:
   if (opt && sc_moved(C)) return;
   edge_costs(C, 1);
   if (threadIdx.x == 0) {  // the expand edge's interpolation data, for the leader (published with SC_EXPAND)
-    for (int j = 0; j < NJ; ++j) { R.ex.ext[j] = g_L.eg_target[0][j]; R.ex.step[j] = g_L.eg_step[0][j]; R.ex.end[j] = g_L.eg_end[0][j]; }
-    for (int k = 0; k < 3; ++k) R.ex.acc[k] = g_L.eg_acc[0][k];
+    if (!opt) {  // (read by scout_pre_publish; a post-solution pass sends them from the batch, sc_early_send)
+      for (int j = 0; j < NJ; ++j) { R.ex.ext[j] = g_L.eg_target[0][j]; R.ex.step[j] = g_L.eg_step[0][j]; R.ex.end[j] = g_L.eg_end[0][j]; }
+      for (int k = 0; k < 3; ++k) R.ex.acc[k] = g_L.eg_acc[0][k];
+    }
     R.ex.ok = 1;
   }
   // the near set of the edge's end (x_new if the edge is valid) is scanned while the helpers check the edge.
@@ -5690,12 +5776,17 @@ redo:
     edge_costs(C, 2);
     [[clang::always_inline]] edge_validity(C, 2, false, P_XEXPAND, OV_NONE, t);
   } else {
-    [[clang::always_inline]] edge_validity(C, 1, false, P_XEXPAND, opt ? OV_NEAR_EXPAND : OV_NONE, t);
+    // (post-solution: R.ex and the edge's start, target and sums go out under the job, sc_early_send)
+    [[clang::always_inline]] edge_validity(C, 1, false, P_XEXPAND, opt ? OV_NEAR_EXPAND : OV_NONE, t, -1,
+                                           opt ? EARLY_EXPAND : EARLY_NONE, par);
   }
+  if (opt) sc_first_send(C, EARLY_EXPAND, par, 1);
   if (threadIdx.x == 0) {
-    for (int j = 0; j < NJ; ++j) { R.e[0].s[j] = g_L.eg_start[0][j]; R.e[0].g[j] = g_L.eg_target[0][j]; }
-    for (int k = 0; k < 3; ++k) R.e[0].acc[k] = g_L.eg_acc[0][k];
-    R.e[0].first = g_L.eg_first[0];
+    if (!opt) {  // (read by scout_pre_publish; a post-solution pass sends them from the batch)
+      for (int j = 0; j < NJ; ++j) { R.e[0].s[j] = g_L.eg_start[0][j]; R.e[0].g[j] = g_L.eg_target[0][j]; }
+      for (int k = 0; k < 3; ++k) R.e[0].acc[k] = g_L.eg_acc[0][k];
+      R.e[0].first = g_L.eg_first[0];
+    }
     const int f = g_L.eg_first[0];
     g_L.ext_nn = f > S.n_pts;
     if (g_L.ext_nn) {
@@ -5715,10 +5806,6 @@ redo:
     XB = uni(g_L.found);
     rp++;
     goto redo;
-  }
-  if (opt) {
-    sc_copy_out(sb, par, &R.e[0], sizeof(ScoutEdge));
-    sc_copy_out(sb, par, &R.ex, sizeof(ScoutExpand));
   }
   if (spec_conn && uni(g_L.ext_nn)) {
     // before the first solution the iteration goes on with connect (connectGraphs): x_new is the expand edge's
@@ -5764,7 +5851,9 @@ redo:
     scout_pre_publish(C, par, tag, true);
     return;
   }
-  if (sc_stale(C, tag)) {
+  // (R.e[0] and R.ex are on their way: sc_early_send under the job, sc_first_send after it; staleness as read in the
+  // job's last collection round)
+  if (uni(g_L.sc_stale_f)) {
     sc_copy_out(sb, par, &R.nr, sizeof(ScoutNear));
     sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
     sc_publish(C, par, tag, SC_DONE);
@@ -5787,57 +5876,65 @@ redo:
     R.nr.nk = g_L.nk; R.nr.n_lo = g_L.n_lo; R.nr.n_hi = g_L.n_hi;
     R.nr.X = X; R.nr.t = t; R.nr.ok = 1;
   }
-  __syncthreads();
-  sc_copy_out(sb, par, &R.nr, sizeof(ScoutNear));
-  sc_publish(C, par, tag, SC_NEAR);
-  SC_PHASE(3);
-  TR();
-  if (sc_moved(C)) return;
   // choose_parent's candidate edges (all needed ones checked: the job computes every tile)
   if (threadIdx.x < 64) {
     const int E = choose_prefix();
     if (threadIdx.x == 0) {
       g_L.cnt = E;
       g_L.found = -1;
+      R.n_choose = E;  // (sent with the candidates' early words, under the job)
     }
   }
   __syncthreads();
+  // SC_NEAR's stores are issued first, then the candidates' row loads: the stage's drain and the rows share one memory
+  // round trip, and sc_publish's barrier is the one the batch needs before edge_costs
+  sc_copy_out(sb, par, &R.nr, sizeof(ScoutNear));
   const int E = uni(g_L.cnt);
+  if (threadIdx.x < E) {
+    const int e = threadIdx.x;
+    NodeRef nd;
+    load_node(C, t, g_L.lo_i[e], &nd);
+    for (int j = 0; j < NJ; ++j) { g_L.eg_start[e][j] = nd.q[j]; g_L.eg_target[e][j] = g_L.xn.q[j]; }
+    for (int k = 0; k < 3; ++k) g_L.eg_base[e][k] = nd.c[k];
+    g_L.eg_near[e] = nd.id;
+  } else if (threadIdx.x >= 64 && (int)threadIdx.x - 64 < min(g_L.n_hi, MAXE)) {
+    // wave 1: the hi list's rows for the rewire stage, final with the near set (a node's configuration never changes;
+    // its cost and parent only steer which edges the scout checks, and the leader takes a result by the edge's bits)
+    const TreeDev& T = C.Q.tr[t];
+    const int i = (int)threadIdx.x - 64, v = g_L.hi_i[i], cap = g_L.S.cap;
+    BCHK(v, cap, __LINE__, t);
+    double q[NJ];
+    for (int j = 0; j < NJ; ++j) q[j] = T.q[(size_t)j * cap + v];
+    const double c0 = T.cost[v];
+    const int pv = T.parent[v];
+    for (int j = 0; j < NJ; ++j) g_L.sc_hq[i][j] = q[j];
+    g_L.sc_hc[i] = c0;
+    g_L.sc_hp[i] = pv;
+  }
+  sc_publish(C, par, tag, SC_NEAR);
+  SC_PHASE(3);
+  TR();
+  if (sc_moved(C)) return;
   if (E > 0) {
-    if (threadIdx.x < E) {
-      const int e = threadIdx.x;
-      NodeRef nd;
-      load_node(C, t, g_L.lo_i[e], &nd);
-      for (int j = 0; j < NJ; ++j) { g_L.eg_start[e][j] = nd.q[j]; g_L.eg_target[e][j] = g_L.xn.q[j]; }
-      for (int k = 0; k < 3; ++k) g_L.eg_base[e][k] = nd.c[k];
-      g_L.eg_near[e] = nd.id;
-    }
-    __syncthreads();
     edge_costs(C, E);
     if (threadIdx.x < E) g_L.eg_need[threadIdx.x] = g_L.eg_cost[threadIdx.x][0] <= g_L.xn.c[0];
     for (int e = E + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
     __syncthreads();
-    [[clang::always_inline]] edge_validity(C, E, false, P_XCHOOSE);
-    if (threadIdx.x < E) {
-      const int e = threadIdx.x;
-      ScoutEdge& w = R.e[SCOUT_CHOOSE0 + e];
-      for (int j = 0; j < NJ; ++j) { w.s[j] = g_L.eg_start[e][j]; w.g[j] = g_L.eg_target[e][j]; }
-      for (int k = 0; k < 3; ++k) w.acc[k] = g_L.eg_acc[e][k];
-      w.first = g_L.eg_need[e] ? g_L.eg_first[e] : -1;
-    }
+    // the candidates' start, target and sums and the counts go out under the job, only {first, pad} after it; nothing
+    // on the scout reads R.e[SCOUT_CHOOSE0 ..], so there is no LDS copy of them
+    [[clang::always_inline]] edge_validity(C, E, false, P_XCHOOSE, OV_NONE, 0, -1, EARLY_CHOOSE, par);
+    sc_first_send(C, EARLY_CHOOSE, par, E);
     if (threadIdx.x < 64) {  // the first needed candidate that is free (ballot: E <= 20)
       const bool fr = (int)threadIdx.x < E && g_L.eg_need[threadIdx.x] && g_L.eg_first[threadIdx.x] > S.n_pts;
       const unsigned long long fm = __ballot(fr);
-      if (threadIdx.x == 0) {
-        R.n_choose = E;
-        if (fm) g_L.found = (int)__builtin_ctzll(fm);
-      }
+      if (threadIdx.x == 0 && fm) g_L.found = (int)__builtin_ctzll(fm);
     }
-    __syncthreads();
+    // (sc_publish's barrier orders g_L.found; the staleness word was read in the job's last collection round)
+    if (uni(g_L.sc_stale_f)) { sc_publish(C, par, tag, SC_DONE); return; }
+  } else {
+    sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
+    if (sc_stale(C, tag)) { sc_publish(C, par, tag, SC_DONE); return; }
   }
-  sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
-  sc_copy_out(sb, par, &R.e[SCOUT_CHOOSE0], E * (int)sizeof(ScoutEdge));
-  if (sc_stale(C, tag)) { sc_publish(C, par, tag, SC_DONE); return; }
   sc_publish(C, par, tag, SC_CHOOSE);
   SC_PHASE(4);
   TR();
@@ -5865,39 +5962,42 @@ redo:
   if (!uni(g_L.ext_nn || g_L.ext_bp)) { sc_end(C, par, tag, opt); return; }
   if (sc_moved(C)) return;
   // rewire's candidate edges (rewire())
-  const TreeDev& T = C.Q.tr[t];
-  rewire_count(T);
+  // (rewire_count's test and the candidates' rows from the hi list's rows in LDS, loaded with choose's: no memory
+  // round trip between the via chain and the rewire job.  Unlike rewire_count the count is clamped to the rows held,
+  // min(n_hi, MAXE), on purpose: it only steers which edges the scout checks, and a near_set<20> list is within it)
+  if (threadIdx.x < 64) {
+    const int n = g_L.nk, lane = threadIdx.x;
+    const int m = min(n >= S.max_near ? S.max_near : n, min(g_L.n_hi, MAXE));
+    const bool ok = lane < m && g_L.xn.c[0] < g_L.sc_hc[g_L.n_hi - 1 - lane];
+    const int c = __popcll(__ballot(ok));
+    if (lane == 0) g_L.cnt = c;
+  }
+  __syncthreads();
   const int cnt = uni(g_L.cnt);
   if (cnt > 0) {
-    if (threadIdx.x < cnt) {
-      const int e = threadIdx.x, v = g_L.hi_i[g_L.n_hi - 1 - e];
-      NodeRef nd;
-      load_node(C, t, v, &nd);
-      for (int j = 0; j < NJ; ++j) { g_L.eg_start[e][j] = g_L.xn.q[j]; g_L.eg_target[e][j] = nd.q[j]; }
+    if (threadIdx.x < cnt * NJ) {
+      const int e = threadIdx.x / NJ, j = threadIdx.x - e * NJ;
+      g_L.eg_start[e][j] = g_L.xn.q[j];
+      g_L.eg_target[e][j] = g_L.sc_hq[g_L.n_hi - 1 - e][j];
+    } else if (threadIdx.x >= 256 && threadIdx.x < 256 + cnt) {
+      const int e = threadIdx.x - 256;
       for (int k = 0; k < 3; ++k) g_L.eg_base[e][k] = g_L.xn.c[k];
-      g_L.eg_near[e] = v;
+      g_L.eg_near[e] = g_L.hi_i[g_L.n_hi - 1 - e];
     }
     __syncthreads();
     edge_costs(C, cnt);
     if (threadIdx.x < cnt) {
-      const int e = threadIdx.x, v = g_L.eg_near[e];
-      g_L.eg_need[e] = (v != g_L.xn.parent) && (T.parent[v] != 0) && (g_L.eg_cost[e][0] < T.cost[v]);
+      const int e = threadIdx.x, v = g_L.eg_near[e], h = g_L.n_hi - 1 - e;
+      g_L.eg_need[e] = (v != g_L.xn.parent) && (g_L.sc_hp[h] != 0) && (g_L.eg_cost[e][0] < g_L.sc_hc[h]);
     }
     for (int e = cnt + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
+    if (threadIdx.x == 0) R.n_rewire = cnt;  // (sent with the candidates' early words, under the job)
     __syncthreads();
-    [[clang::always_inline]] edge_validity(C, cnt, false, P_XREWIRE);
-    if (threadIdx.x < cnt) {
-      const int e = threadIdx.x;
-      ScoutEdge& w = R.e[SCOUT_REWIRE0 + e];
-      for (int j = 0; j < NJ; ++j) { w.s[j] = g_L.eg_start[e][j]; w.g[j] = g_L.eg_target[e][j]; }
-      for (int k = 0; k < 3; ++k) w.acc[k] = g_L.eg_acc[e][k];
-      w.first = g_L.eg_need[e] ? g_L.eg_first[e] : -1;
-    }
-    if (threadIdx.x == 0) R.n_rewire = cnt;
-    __syncthreads();
+    [[clang::always_inline]] edge_validity(C, cnt, false, P_XREWIRE, OV_NONE, 0, -1, EARLY_REWIRE, par);
+    sc_first_send(C, EARLY_REWIRE, par, cnt);
+  } else {
+    sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
   }
-  sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
-  sc_copy_out(sb, par, &R.e[SCOUT_REWIRE0], cnt * (int)sizeof(ScoutEdge));
   sc_publish(C, par, tag, SC_DONE);
   SC_PHASE(6);
   TR();

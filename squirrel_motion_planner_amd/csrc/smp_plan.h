@@ -1,5 +1,6 @@
 // Device-resident BiRRT* planner state (one workgroup per query).  Shared by smp_kernels.hip and the host.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "smp_types.h"
@@ -186,6 +187,10 @@ struct ScoutEdge {             // one candidate edge: interpolation start / targ
   double acc[3];               // segment-norm sums (edge_costs' eg_acc; cost = start node's cost + acc)
   int first, pad;              // first: as eg_first (n_pts + 1 = free), -1 = not checked
 };
+// A scout sends s, g and acc while the edge's collision job runs and the last 8-byte word, {first, pad}, after it: no
+// word is stored twice within a stage, so `first` must be alone with its pad in the struct's last word.
+static_assert(offsetof(ScoutEdge, first) % 8 == 0 && sizeof(ScoutEdge) - offsetof(ScoutEdge, first) == 8,
+              "ScoutEdge: {first, pad} is the last 8-byte word");
 struct ScoutExpand {           // stage SC_EXPAND: the expand edge's interpolation data (edge_costs of edge 0)
   double ext[NJ];              // step target (stepTowardsRandSample from the nearest node towards the sample)
   double step[NJ], end[NJ];    // interpolation step and end point
