@@ -341,6 +341,19 @@ struct SamplerLds {
 #endif
 constexpr int PLAN_CT = SMP_PLAN_CT;  // configurations per collision tile of the planner
 constexpr int PATCH_K = 32;           // leader: recently appended nodes kept in LDS per tree (power of two)
+// A via chain's batch (via_chain): wave 0 takes up to VIA_B steps and leaves one row per step; the workgroup then forms
+// the steps' segment norms (per wave, in seg), their ordered sums (acc) and the node rows.
+constexpr int VIA_B = 16;
+struct ViaRow { double cur[NJ], ox[NJ], stp[NJ], end[NJ]; };  // a step's start, target, interpolation step, end
+struct ViaLds {
+  double seg[BLOCK / 64][MAX_PTS][3];  // wave w's segment norms of the step it is summing
+  ViaRow row[VIA_B];
+  double acc[VIA_B][3];
+  int n, fin;                          // rows of the batch; the last row 1 = reached the target, 2 = found the via list full
+};
+constexpr int VIA_WORDS = sizeof(ViaNode) / 8;
+static_assert(sizeof(ViaNode) == 8 * (3 * NJ + 3 + 1), "ViaNode as 8-byte words: q, c, e_start, e_target, {id, parent}");
+static_assert(VIA_B * VIA_WORDS <= BLOCK, "one ViaNode word per thread");
 struct PlanLds {
   QState S;
   union {
@@ -350,6 +363,7 @@ struct PlanLds {
     } tile;
     JobLds job;  // job mode: the leader's LDS copy of its published job + one job tile
     double seg[MAXE][MAX_PTS][3];
+    ViaLds via;  // (a chain runs between the edge batches: their seg rows are free)
     SmpLds smp;
     SamplerLds smpl;  // a helper block of plan_kernel that runs the run-ahead sampler
   } u;
@@ -464,6 +478,7 @@ struct PlanLds {
 // The planner's LDS objects live at namespace scope so that every device function addresses them as LDS
 // (ds_read/ds_write) rather than through generic pointers.
 __shared__ PlanLds g_L;
+static_assert(sizeof(ViaLds) <= sizeof(g_L.u.seg), "a via chain's batch lies within the union's edge rows");
 
 struct Ctx {
   SceneDev sc;
@@ -2207,6 +2222,22 @@ __device__ __forceinline__ void seg_norms(unsigned rm, const double* st, const d
   t = sqrt(t); r = sqrt(r); p = sqrt(p);
 }
 
+// Column k of the rows seg[0 .. N) of LDS added in order from 0.0, where the rows from np on hold +0.0: the reference's
+// sum of an edge's np segment norms, bit for bit.  acc + 0.0 is acc for every acc but -0.0, and acc is never -0.0: it
+// starts at +0.0 and takes square roots of sums of squares, none below +0.0.  All loads are issued before the first add
+// (a runtime-bound loop, or loads under `s < np`, waited one LDS round trip per term), and the adds are one straight
+// line: `if (s < np) acc += t[s]` compiled to two selects around every add, on the dependent chain.
+template <int N>
+__device__ __forceinline__ double ordered_sum(const double (*seg)[3], int k) {
+  double t[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) t[i] = seg[i][k];
+  double acc = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) acc += t[i];
+  return acc;
+}
+
 // connectNodesInterpolation + compute_edge_cost_interpolation (birrt_star.cpp:4380-4440, 4443-4526,
 // 4162-4242) for E <= MAXE edges eg_start -> eg_target, base costs eg_base.  Segment norms in parallel,
 // ordered sums per edge.  Fills eg_step, eg_end (the child configuration) and eg_cost.
@@ -3810,7 +3841,13 @@ __device__ bool step_towards(const RobotDev* rb, const double* nn, double* x, do
 // divisions run once, lane l dividing joint l % 8's difference, and the revolute / prismatic square roots once, even
 // and odd lanes; every lane takes the results back by v_readlane.  nn_l / x_l are lane l's copies of nn[l % 8] and
 // x[l % 8] (kept beside the arrays: picking an array element by lane compiles to a private-memory round trip); x_l
-// is updated with x.  The operations and their order per value are step_towards_m's.
+// is updated with x.  The operations and their order per value are step_towards_m's, with one exception in form only:
+// a term d enters the revolute and the prismatic sum as fma(d, m, s), m = 1.0 for the joint's own kind and 0.0 for the
+// other (wave-uniform constants of the model), where step_towards_m adds the select `own kind ? d : 0.0`.
+// fma(d, 1.0, s) rounds d + s once, as the add does; fma(d, 0.0, s) is s + 0.0 = s for a finite d (d * 0.0 = +0.0, d
+// being a square; s is a sum of squares, never -0.0), and the terms are finite: differences of configurations, and
+// c * c only behind the `done` select that keeps a division by a zero length out.  One operation per sum and term
+// instead of a 64-bit select and an add.
 __device__ __forceinline__ bool step_towards_w(unsigned rm, const double* nn, double* x, double f, int lane, double nn_l,
                                                double& x_l) {
   double ed[NJ], srev = 0.0, spr = 0.0;
@@ -3819,8 +3856,8 @@ __device__ __forceinline__ bool step_towards_w(unsigned rm, const double* nn, do
     const bool rv = (rm >> j) & 1u;
     ed[j] = x[j] - nn[j];
     const double d = ed[j] * ed[j];
-    srev += rv ? d : 0.0;
-    spr += rv ? 0.0 : d;
+    srev = __builtin_fma(d, rv ? 1.0 : 0.0, srev);
+    spr = __builtin_fma(d, rv ? 0.0 : 1.0, spr);
   }
   const double l2 = sqrt((lane & 1) ? spr : srev);
   const double lrev = readlane_d(l2, 0), lpr = readlane_d(l2, 1);
@@ -3836,8 +3873,8 @@ __device__ __forceinline__ bool step_towards_w(unsigned rm, const double* nn, do
     const double c = f * readlane_d(ql, j);
     ext[j] = done ? 0.0 : nn[j] + c;
     const double cc = done ? 0.0 : c * c;
-    srev += rv ? cc : 0.0;
-    spr += rv ? 0.0 : cc;
+    srev = __builtin_fma(cc, rv ? 1.0 : 0.0, srev);
+    spr = __builtin_fma(cc, rv ? 0.0 : 1.0, spr);
   }
   const double e2 = sqrt((lane & 1) ? spr : srev);
   const double elr = srev == 0.0 ? 1000.0 : readlane_d(e2, 0);
@@ -3855,144 +3892,194 @@ __device__ __forceinline__ bool step_towards_w(unsigned rm, const double* nn, do
 // Stepping loop shared by choose_parent / connectGraphs: from `cur` towards `target` with
 // unconstraint_extend_step_factor, collecting via nodes (ids nn_t, nn_t+1, ...) until the target is
 // reached; the last edge becomes `sel` (id nn_t at that point).  No collision checks (reference behaviour).
-// Wave 0 alone, the chain's state in registers (every lane holds the same values; lane s of the first half forms
-// segment s of a step's edge cost as edge_costs does): no barrier per step.  On return g_L.cur, ox, reached, nn_t,
-// n_via and edge slot 0 hold what the last step left, as a step-by-step block loop would.
-__device__ __noinline__ void via_chain_w(const Ctx& C, const double* target) {
-  const int lane = lane_id(), s = lane & 31;
-  const int np = g_L.S.n_pts, via_cap = g_L.S.via_cap;
+// Only the stepping is serial (a step starts where the last one ended), so wave 0 takes the steps alone, VIA_B at a
+// time, and leaves one ViaRow per step (via_steps_w); everything else about a step depends on its row only and is
+// formed by the whole workgroup afterwards (via_costs).
+//
+// Wave 0: up to VIA_B steps from g_L.cur, the chain's state in registers (every lane holds the same values, lane l
+// also joint l % 8's as step_towards_w wants them): no barrier per step.  A batch ends with the step that reaches the
+// target (fin = 1), with the step that finds the via list full (fin = 2: n_via >= via_cap, its node is not stored) or
+// after VIA_B steps (fin = 0: via_costs moves g_L.cur to the last step's end and the next batch goes on from there).
+__device__ __noinline__ void via_steps_w(const double* target) {
+  ViaLds& V = g_L.u.via;
+  const int lane = lane_id();
+  const int np = g_L.S.n_pts, room = g_L.S.via_cap - g_L.n_via;  // steps of this batch that find room in the via list
   const double f = g_L.S.step;
-  double cur[NJ], cc[3], tg[NJ], ox[NJ], stp[NJ], end[NJ], acc[3], cost[3];
-  int cid = g_L.cur.id, cpar = g_L.cur.parent;
+  double cur[NJ], tg[NJ], ox[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) { cur[j] = g_L.cur.q[j]; tg[j] = target[j]; }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) cc[k] = g_L.cur.c[k];
-  int nn_t = g_L.nn_t, n_via = g_L.n_via, nsteps = 0;
   const unsigned rm = rev_mask(&g_rb);
   double cur_l = g_L.cur.q[lane & 7], ox_l;  // lane l's copies of cur[l % 8] / ox[l % 8] (step_towards_w)
   const double tg_l = target[lane & 7];
   static_assert(NJ == 8, "lane copies of the joints");
-#ifdef SMP_VIA_PROF  // lane-0 clocks into prof[28..31]: entry, stepping, edge costs, calls
-  unsigned long long _v0 = wall_clock64(), _v1;
-#define VIA_CLK(k) { _v1 = wall_clock64(); if (lane == 0) g_L.S.prof[k] += _v1 - _v0; _v0 = _v1; }
-#else
-#define VIA_CLK(k)
-#endif
-  VIA_CLK(31);
-  bool reached, overflow = false;
-  double lst[NJ], lcc[3];  // the last step's edge start and base cost (edge slot 0)
+  int r = 0, fin = 0;
   for (;;) {
-    ++nsteps;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) ox[j] = tg[j];
     ox_l = tg_l;
-    reached = step_towards_w(rm, cur, ox, f, lane, cur_l, ox_l);
-    // the step of the edge: lane l divides joint l % 8's difference (one division for the wave)
+    const bool reached = uni(step_towards_w(rm, cur, ox, f, lane, cur_l, ox_l));
+    // the step of the edge and its end: lane l divides joint l % 8's difference (one division for the wave)
     const double ql = (ox_l - cur_l) / double(np);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      stp[j] = readlane_d(ql, j);
-      end[j] = cur[j] + np * stp[j];
+    const double end_l = cur_l + np * ql;
+    if (lane < NJ) {
+      ViaRow& R = V.row[r];
+      R.cur[lane] = cur_l; R.ox[lane] = ox_l; R.stp[lane] = ql; R.end[lane] = end_l;
     }
-    VIA_CLK(28);
-    // the segment norms: with np <= 21, lane 21 k + s takes norm k (total, revolute, prismatic) of segment s, one
-    // square root for the wave; else lane s all three of segment s
-    if (np <= 21) {
-      const int k = lane / 21, sg = lane - 21 * k;
-      double t, r, p;
-      seg_terms(rm, cur, stp, sg, t, r, p);
-      const double v = sqrt(k == 0 ? t : k == 1 ? r : p);
-      if (sg < np && k < 3) g_L.u.seg[0][sg][k] = v;
-    } else {
-      double t, r, p;
-      seg_norms(rm, cur, stp, s, t, r, p);
-      if (lane < np) { g_L.u.seg[0][lane][0] = t; g_L.u.seg[0][lane][1] = r; g_L.u.seg[0][lane][2] = p; }
-    }
-    VIA_CLK(29);
-    // the ordered sums (edge_costs' third stage): lanes 0..2 sum the segments through LDS (in order; one wave, so
-    // its LDS writes are seen by its later reads), and every lane takes the three sums by v_readlane
-    double al = 0.0;
-    if (lane < 3) {
-      double sg[MAX_PTS];
+    ++r;
+    if (reached) { fin = 1; break; }
+    if (r > room) { fin = 2; break; }
+    if (r == VIA_B) break;
 #pragma unroll
-      for (int i = 0; i < MAX_PTS; ++i) sg[i] = g_L.u.seg[0][i][lane];  // (unconditional: see edge_costs)
-#pragma unroll
-      for (int i = 0; i < MAX_PTS; ++i)
-        if (i < np) al += sg[i];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = readlane_d(al, k);
-    VIA_CLK(30);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) cost[k] = cc[k] + acc[k];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) lst[j] = cur[j];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) lcc[k] = cc[k];
-    if (reached) break;
-    const int id = nn_t++;
-    if (n_via >= via_cap) { overflow = true; reached = true; break; }
-    if (lane == 0) {
-      ViaNode& v = C.Q.via[n_via];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { v.q[j] = end[j]; v.e_start[j] = cur[j]; v.e_target[j] = ox[j]; }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) v.c[k] = cost[k];
-      v.id = id;
-      v.parent = cid;
-    }
-    ++n_via;
-    cpar = cid;
-    cid = id;
-    cur_l = cur_l + np * ql;  // end[l % 8]
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) cur[j] = end[j];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) cc[k] = cost[k];
+    for (int j = 0; j < NJ; ++j) cur[j] = readlane_d(end_l, j);
+    cur_l = end_l;
   }
-#undef VIA_CLK
-  if (lane == 0) {
-    QState& S = g_L.S;
-    S.prof[P_NVIA] += nsteps;
-    if (overflow) { S.status = -7; S.phase = 2; }
-    else {
-      NodeRef& g = g_L.sel;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) { g.q[j] = end[j]; g_L.sel_start[j] = cur[j]; g_L.sel_target[j] = ox[j]; }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) g.c[k] = cost[k];
-      g.id = nn_t;
-      g.parent = cid;
+  if (lane == 0) { V.n = r; V.fin = fin; }
+}
+
+// via_costs' prefix from step R on: c = the cost before step R, on return after the batch's last step n - 1, with the
+// cost before that step in `base` and its sum in `last`.  n and nv are wave-uniform: nested scalar branches, one per
+// step taken, the sums a[] in registers (a loop left by `break` was rolled up over an array in private memory).
+template <int R>
+__device__ __forceinline__ void via_prefix(const double* a, int n, int nv, double* vc, double& c, double& base, double& last) {
+  if constexpr (R < VIA_B) {
+    if (R < n) {
+      base = c;
+      last = a[R];
+      c = base + last;
+      if (R < nv) vc[R * VIA_WORDS] = c;
+      via_prefix<R + 1>(a, n, nv, vc, c, base, last);
     }
-    g_L.reached = 1;
-    g_L.nn_t = nn_t;
-    g_L.n_via = n_via;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      g_L.cur.q[j] = cur[j];
-      g_L.ox[j] = ox[j];
-      g_L.eg_start[0][j] = lst[j];
-      g_L.eg_target[0][j] = ox[j];
-      g_L.eg_step[0][j] = stp[j];
-      g_L.eg_end[0][j] = end[j];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      g_L.cur.c[k] = cc[k];
-      g_L.eg_base[0][k] = lcc[k];
-      g_L.eg_acc[0][k] = acc[k];
-      g_L.eg_cost[0][k] = cost[k];
-    }
-    g_L.cur.id = cid;
-    g_L.cur.parent = cpar;
   }
 }
+
+// The workgroup, after a batch of wave 0's and a barrier: step r's segment norms and their ordered sums (edge_costs'
+// second and third stage) on wave r % 8, the nodes' costs as a prefix over the steps in step order (cost_r =
+// cost_{r-1} + acc_r from g_L.cur.c, the additions a step-by-step loop makes), the ViaNode rows of the steps that
+// did not end the chain (ids nn_t, nn_t + 1, ..., each the parent of the next) one 8-byte word per thread, and the state a
+// step-by-step block loop would leave: g_L.cur (the last step's start and base cost once the chain has ended, else the
+// next batch's start), nn_t, n_via, and after the chain's last step ox, reached, edge slot 0 and `sel` (not on a full
+// via list: status -7).  Returns whether the chain has ended.  Ends with a barrier: C.Q.via and the state are
+// stored by several waves.
+__device__ __noinline__ bool via_costs(const Ctx& C) {
+  ViaLds& V = g_L.u.via;
+  QState& S = g_L.S;
+#ifdef SMP_VIA_PROF  // thread-0 clocks into prof[29..30]: norms and sums to the barrier, costs and state to the barrier
+  unsigned long long _v0 = threadIdx.x == 0 ? wall_clock64() : 0;
+#define VIA_CLK(k) if (threadIdx.x == 0) { const unsigned long long _v1 = wall_clock64(); S.prof[k] += _v1 - _v0; _v0 = _v1; }
+#else
+#define VIA_CLK(k)
+#endif
+  const int n = uni(V.n), fin = uni(V.fin), np = uni(S.n_pts);
+  const int nv = fin ? n - 1 : n;  // steps that become via nodes
+  const int n_via0 = uni(g_L.n_via), nn_t0 = uni(g_L.nn_t), cid0 = uni(g_L.cur.id), cpar0 = uni(g_L.cur.parent);
+  const int w = wave_id(), lane = lane_id();
+  const unsigned rm = rev_mask(&g_rb);
+  for (int r = w; r < n; r += BLOCK / 64) {
+    double cur[NJ], stp[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { cur[j] = V.row[r].cur[j]; stp[j] = V.row[r].stp[j]; }
+    // the segment norms: with np <= 21, lane 21 k + s takes norm k (total, revolute, prismatic) of segment s, one
+    // square root for the wave; else lane s all three of segment s.  The rows from np on get +0.0 (ordered_sum); then
+    // lanes 0..2 sum the rows through LDS (one wave, so its LDS writes are seen by its later reads)
+    if (np <= 21) {
+      const int k = lane / 21, sg = lane - 21 * k;
+      double t, rr, p;
+      seg_terms(rm, cur, stp, sg, t, rr, p);
+      const double v = sqrt(k == 0 ? t : k == 1 ? rr : p);
+      if (k < 3) V.seg[w][sg][k] = sg < np ? v : 0.0;
+      if (lane < 3) V.acc[r][lane] = ordered_sum<21>(V.seg[w], lane);
+    } else {
+      double t, rr, p;
+      seg_norms(rm, cur, stp, lane & 31, t, rr, p);
+      const bool in = lane < np;
+      if (lane < MAX_PTS) { V.seg[w][lane][0] = in ? t : 0.0; V.seg[w][lane][1] = in ? rr : 0.0; V.seg[w][lane][2] = in ? p : 0.0; }
+      if (lane < 3) V.acc[r][lane] = ordered_sum<MAX_PTS>(V.seg[w], lane);
+    }
+  }
+  __syncthreads();
+  VIA_CLK(29);
+  {  // the nodes' words other than the costs: q = the step's end, e_start, e_target, {id, parent} (stored after the
+     // barrier, which would wait for them)
+    const int r = threadIdx.x / VIA_WORDS, wd = threadIdx.x - r * VIA_WORDS;
+    if (r < nv && (wd < NJ || wd >= NJ + 3)) {
+      const unsigned long long* R = reinterpret_cast<const unsigned long long*>(&V.row[r]);
+      unsigned long long v;
+      if (wd < NJ) v = R[3 * NJ + wd];
+      else if (wd < 2 * NJ + 3) v = R[wd - (NJ + 3)];
+      else if (wd < 3 * NJ + 3) v = R[NJ + wd - (2 * NJ + 3)];
+      else {
+        const int id = nn_t0 + r, parent = r ? id - 1 : cid0;
+        v = (unsigned long long)(unsigned)id | ((unsigned long long)(unsigned)parent << 32);
+      }
+      reinterpret_cast<unsigned long long*>(&C.Q.via[n_via0 + r])[wd] = v;
+    }
+  }
+  if (threadIdx.x < 3) {
+    const int k = threadIdx.x;
+    // the costs, a prefix over the batch's n steps in step order; every step but one that ended the chain stores its
+    // node's cost.  The sums are loaded before the first add (the rows past n are read and not added)
+    double a[VIA_B];
+#pragma unroll
+    for (int i = 0; i < VIA_B; ++i) a[i] = V.acc[i][k];
+    double c = g_L.cur.c[k], base = c, last = 0.0;
+    via_prefix<0>(a, n, nv, &C.Q.via[n_via0].c[k], c, base, last);
+    if (fin) {  // the last step's edge: base cost, sums, cost; g_L.cur keeps the step's start
+      g_L.cur.c[k] = base;
+      g_L.eg_base[0][k] = base;
+      g_L.eg_acc[0][k] = last;
+      g_L.eg_cost[0][k] = c;
+      if (fin == 1) g_L.sel.c[k] = c;
+    } else {
+      g_L.cur.c[k] = c;
+    }
+  } else if (threadIdx.x >= 64 && threadIdx.x < 64 + NJ) {
+    const int j = threadIdx.x - 64;
+    const ViaRow& R = V.row[n - 1];
+    if (fin) {
+      const double st = R.cur[j], ox = R.ox[j], en = R.end[j];
+      g_L.cur.q[j] = st;
+      g_L.ox[j] = ox;
+      g_L.eg_start[0][j] = st;
+      g_L.eg_target[0][j] = ox;
+      g_L.eg_step[0][j] = R.stp[j];
+      g_L.eg_end[0][j] = en;
+      if (fin == 1) { g_L.sel.q[j] = en; g_L.sel_start[j] = st; g_L.sel_target[j] = ox; }
+    } else {
+      g_L.cur.q[j] = R.end[j];
+    }
+  } else if (threadIdx.x == 128) {
+    const int cid = nv ? nn_t0 + nv - 1 : cid0, nn_t = nn_t0 + nv + (fin == 2);
+    S.prof[P_NVIA] += n;
+    g_L.cur.id = cid;
+    g_L.cur.parent = nv == 0 ? cpar0 : nv == 1 ? cid0 : nn_t0 + nv - 2;
+    g_L.n_via = n_via0 + nv;
+    g_L.nn_t = nn_t;
+    if (fin) {
+      g_L.reached = 1;
+      if (fin == 2) { S.status = -7; S.phase = 2; }
+      else { g_L.sel.id = nn_t; g_L.sel.parent = cid; }
+    }
+  }
+  __syncthreads();
+  VIA_CLK(30);
+#undef VIA_CLK
+  return fin != 0;
+}
+
 __device__ void via_chain(const Ctx& C, const double* target) {
   TR();
   PROF_BEGIN();
-  if (threadIdx.x < 64) via_chain_w(C, target);
-  __syncthreads();
+  for (;;) {
+#ifdef SMP_VIA_PROF  // thread-0 clocks into prof[28] (wave 0's steps, to the barrier) and prof[31] (batches)
+    const unsigned long long _v0 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
+    if (threadIdx.x < 64) via_steps_w(target);
+    __syncthreads();
+#ifdef SMP_VIA_PROF
+    if (threadIdx.x == 0) { g_L.S.prof[28] += wall_clock64() - _v0; g_L.S.prof[31] += 100; }
+#endif
+    if (via_costs(C)) break;
+  }
   PROF_END(P_VIA);
   TR();
 }
