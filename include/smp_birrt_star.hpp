@@ -254,6 +254,54 @@ class BiRRTstarPlanner {
     return v != 0;
   }
 
+  // birrt_star.h:103-104 (birrt_star.cpp:6864-6895) for the edge from -> to, interpolated at the planner's collision
+  // density hop by hop of at most one planner step (smp_check_edges): true if every point is free.
+  // last_valid_node_idx is left as the reference leaves it: the last point of a free edge, else the last free point
+  // before the first colliding one (0 when the first point collides).
+  bool isEdgeValid(const vector<double>& from, const vector<double>& to, int& last_valid_node_idx,
+                   bool check_self_collision, bool check_map_collision) {
+    need();
+    last_valid_node_idx = 0;
+    if (from.size() != 8 || to.size() != 8) return false;
+    int64_t first = -1;
+    int32_t n_points = 0;
+    check(smp_check_edges(planner_, from.data(), to.data(), 1, check_self_collision, check_map_collision, &first,
+                          &n_points), "isEdgeValid");
+    last_valid_node_idx = first < 0 ? n_points - 1 : (first > 0 ? (int)first - 1 : 0);
+    return first < 0;
+  }
+
+  // Shortens a trajectory in place (smp_shortcut_path): every waypoint pair within `window` (0: all pairs) is checked
+  // as a dense edge in one launch, the cheapest route through the free ones is kept and the via nodes of its edges are
+  // inserted, so consecutive poses stay at most one planner step apart.  The node calls it between
+  // getJointTrajectoryRef and normalizeTrajectory.  False, trajectory untouched, when the path is blocked (or has
+  // fewer than two poses: there is no edge to check).
+  bool shortcutTrajectory(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
+                          int window = 0) {
+    need();
+    if (trajectory.size() < 2) return false;
+    vector<double> rows;
+    rows.reserve(trajectory.size() * 8);
+    for (size_t i = 0; i < trajectory.size(); ++i) {
+      if (trajectory[i].size() != 8) return false;
+      rows.insert(rows.end(), trajectory[i].begin(), trajectory[i].end());
+    }
+    double* out = nullptr;
+    int64_t n_out = 0;
+    const int st = smp_shortcut_path(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
+                                     check_map_collision, window, &out, &n_out, &shortcut_);
+    if (st == SMP_ERR_NO_SOLUTION) return false;
+    check(st, "shortcutTrajectory");
+    vector<vector<double> > res((size_t)n_out, vector<double>(8));
+    for (int64_t i = 0; i < n_out; ++i)
+      for (int j = 0; j < 8; ++j) res[(size_t)i][(size_t)j] = out[i * 8 + j];
+    smp_buffer_free(out);
+    trajectory.swap(res);
+    return true;
+  }
+  // Counts, costs and timing of the last shortcutTrajectory.
+  const smp_shortcut_info& lastShortcut() const { return shortcut_; }
+
   // birrt_star.cpp:6910-6914 (collision_checker.hpp:123-132, 594-630): appends the colliding self pairs (pair order)
   // and the map-colliding links (name order, disabled links included) of one configuration.
   void getCollisions(const std::vector<double>& jointPositions, std::vector<std::pair<std::string, std::string> >& selfCollisions,
@@ -346,6 +394,7 @@ class BiRRTstarPlanner {
   smp_planner* planner_ = nullptr;
   smp_params params_;
   smp_stats stats_{};
+  smp_shortcut_info shortcut_{};
   double env_x_[2] = {0, 0}, env_y_[2] = {0, 0};
   vector<double> start_, goal_;
   bool self_ = true, map_ = true, ready_ = false;

@@ -37,6 +37,13 @@
  *                              123-132, 594-630): colliding self pairs and map-colliding links of one configuration
  *   smp_check_sequence         the node's keyframe loops over isConfigValid (fold / unfold arm,
  *                              squirrel_8dof_planner.cpp:759-784, 814-823): first invalid pose, one kernel launch
+ *   smp_check_edges            batched BiRRTstarPlanner::isEdgeValid (birrt_star.h:103-104, birrt_star.cpp:6864-6895):
+ *                              every edge interpolated as connectNodesInterpolation does (birrt_star.cpp:4443-4526),
+ *                              hop by hop of at most one planner step -> index of the first colliding point
+ *   smp_shortcut_path          a simplification pass over a finished path (the reference has none: the node resamples
+ *                              getJointTrajectoryRef as it is, squirrel_8dof_planner.cpp:1238-1248): every waypoint
+ *                              pair as one dense edge check, then the cheapest route (edge cost as DH:128-156)
+ *   smp_buffer_free            releases smp_shortcut_path's output
  *   smp_normalize_trajectory   Planner::normalizeTrajectory (squirrel_8dof_planner.cpp:1557-1637), host only
  *   smp_ik_solve               BiRRTstarPlanner::getFullPoseFromEEPose (birrt_star.cpp:1627-1686) ->
  *                              RobotController::run_VDLS_Control_Connector (control_laws.cpp:3283-3712):
@@ -293,6 +300,54 @@ int smp_get_collisions(smp_planner* p, const double q[8], int32_t* self_pairs, i
 /* n poses, row-major n x 8: *first_invalid = index of the first pose in collision, -1 if all are valid. */
 int smp_check_sequence(smp_planner* p, const double* q_rows, int64_t n, int check_self, int check_map,
                        int64_t* first_invalid);
+/* Dense edge checks.  The density rule, for an edge a -> b (8 values each), the planner's num_traj_segments n and
+ * step_factor f: d[j] = b[j] - a[j]; L_rev = sqrt(sum of d[j]^2 over the revolute joints), L_pr the same over the
+ * prismatic ones (each summed for j ascending); m = max(1, ceil(max(L_rev, L_pr) / f)) hops of at most one planner
+ * step; M = n * m; point k (0..M) is a[j] + k * (d[j] / M), the quotient formed first, without contraction.  For m = 1
+ * these are bit for bit the n + 1 configurations of the reference's edge trajectory (birrt_star.cpp:4443-4526); the via
+ * nodes of an edge are its points n, 2n, ..., (m - 1) n.  Coordinates must be finite and an edge may have at most
+ * SMP_EDGE_MAX_POINTS points (SMP_ERR_ARG otherwise). */
+enum {
+  SMP_EDGE_MAX_POINTS = 1 << 20,  /* points of one edge, M + 1 */
+  SMP_EDGE_TABLE_MAX = 1 << 20    /* edges of one smp_check_edges call; waypoints and candidate pairs of one
+                                     smp_shortcut_path call (all pairs: k <= 1448) */
+};
+/* Batched isEdgeValid (birrt_star.cpp:6864-6895): n edges from_rows[i] -> to_rows[i] (row-major n x 8), one kernel
+ * launch.  first_invalid[i] = index of edge i's first colliding point, -1 if the edge is free (the reference's
+ * last_valid_node_idx is then M, else max(first_invalid - 1, 0)); n_points[i] = M + 1 (may be NULL).  Honours
+ * smp_set_disabled_map_links.  n = 0: SMP_OK.  check_map without a scene: SMP_ERR_ARG (a caller asking whether a
+ * trajectory is free of the map must not be answered by the self test alone; smp_check_configs does answer so).
+ * n > SMP_EDGE_TABLE_MAX: SMP_ERR_CAPACITY. */
+int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, int check_self,
+                    int check_map, int64_t* first_invalid, int32_t* n_points);
+
+typedef struct smp_shortcut_info {   /* may be NULL */
+  int64_t n_edges;          /* candidate pairs checked */
+  int64_t n_valid;          /* ... of which free */
+  int64_t configs_checked;  /* points up to and including the first colliding one per edge (smp_stats' convention) */
+  double cost_in;           /* sum of dist(w_i, w_i+1), i ascending */
+  double cost_out;          /* the dynamic program's cost of the chosen route (0 when blocked) */
+  int64_t first_blocked;    /* blocked: the smallest i whose edge (i, i + 1) is invalid; else -1 */
+  double kernel_ms;         /* HIP events around the edge kernel */
+  double total_ms;          /* host clock, call entry to return */
+} smp_shortcut_info;
+/* Shortens a path of k waypoints (row-major k x 8).
+ *  1. Candidates are all pairs (i, j), i < j, j - i <= window (window <= 0: all pairs), adjacent pairs included (the
+ *     scene may have changed since the path was planned); each is one edge of the density rule and all are checked in
+ *     one launch.
+ *  2. dp[0] = 0; for j ascending and i ascending over the valid (i, j): c = dp[i] + dist(w_i, w_j), dist the 8-term sum
+ *     for joints ascending followed by a square root (DH:128-156); the first strict minimum wins.
+ *  3. Output: the chosen waypoints with the via nodes of each chosen edge between them, so every hop is at most one
+ *     planner step and every row is a configuration that was collision-checked (the last waypoint as point M of its
+ *     edges, a + M * (d / M), which can differ from it in the last bit).  *out_waypoints (n_out x 8) is allocated by the
+ *     library: release it with smp_buffer_free.
+ *  4. Waypoint k - 1 not reachable: SMP_ERR_NO_SOLUTION, info->first_blocked set, *out_waypoints = NULL, *n_out = 0.
+ * k < 2: SMP_ERR_ARG (k = 2 is one candidate).  More than SMP_EDGE_TABLE_MAX waypoints or candidates:
+ * SMP_ERR_CAPACITY (bound them with window).  check_map without a scene: SMP_ERR_ARG. */
+int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map, int window,
+                      double** out_waypoints, int64_t* n_out, smp_shortcut_info* info);
+void smp_buffer_free(void* buffer);  /* NULL is allowed */
+
 /* n poses of `dim` values, row-major.  *n_out = rows of the normalized trajectory; with out == NULL only counts,
  * else writes them (SMP_ERR_CAPACITY if out_cap < *n_out).  For dim < 1 or n <= 1 the reference leaves its output
  * untouched: *n_out = 0.  Host only (no GPU needed). */

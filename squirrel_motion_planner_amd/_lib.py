@@ -93,6 +93,15 @@ class SceneBuild(ctypes.Structure):
                 ("bbox_max", _d * 3), ("kernel_ms", _d), ("total_ms", _d)]
 
 
+class ShortcutInfo(ctypes.Structure):
+    """smp_shortcut_info: counts, costs and timing of one smp_shortcut_path call."""
+    _fields_ = [("n_edges", _i64), ("n_valid", _i64), ("configs_checked", _i64), ("cost_in", _d), ("cost_out", _d),
+                ("first_blocked", _i64), ("kernel_ms", _d), ("total_ms", _d)]
+
+
+SMP_EDGE_MAX_POINTS = 1 << 20
+SMP_EDGE_TABLE_MAX = 1 << 20
+
 # (name, restype, argtypes) of every symbol declared in include/smp_gpu.h
 EXPORTS = [
     ("smp_params_default", None, [ctypes.POINTER(Params)]),
@@ -136,6 +145,10 @@ EXPORTS = [
     ("smp_check_sequence", _i, [_p, _pd, _i64, _i, _i, ctypes.POINTER(_i64)]),
     ("smp_get_collisions", _i, [_p, _pd, ctypes.POINTER(ctypes.c_int32), _i, ctypes.POINTER(_i),
                                 ctypes.POINTER(ctypes.c_int32), _i, ctypes.POINTER(_i)]),
+    ("smp_check_edges", _i, [_p, _pd, _pd, _i64, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32)]),
+    ("smp_shortcut_path", _i, [_p, _pd, _i64, _i, _i, _i, ctypes.POINTER(_pd), ctypes.POINTER(_i64),
+                               ctypes.POINTER(ShortcutInfo)]),
+    ("smp_buffer_free", None, [_p]),
     ("smp_normalize_trajectory", _i, [_pd, _i64, _i, _pd, _pd, _i64, ctypes.POINTER(_i64)]),
     ("smp_ik_solve", _i, [_p, ctypes.POINTER(IkRequest), _i, ctypes.POINTER(IkResult)]),
     ("smp_find_goal_pose", _i, [_p, _pd, _pd, _d, _i, _i, _pd, ctypes.POINTER(_i), ctypes.POINTER(GoalSearch)]),

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/smp_gpu.h"
+#include "smp_edges.h"
 #include "smp_host.h"
 #include "smp_ik.h"
 #include "smp_math.h"
@@ -143,6 +144,11 @@ struct smp_planner {
   DBuf<IkOutDev> d_ik_out;
   DBuf<int> d_ik_best;
   DBuf<double> d_path_edges;       // path_edges_kernel output (the path's edges, one copy to the host)
+  // batched dense edge checks (smp_check_edges / smp_shortcut_path): edge table, longest-first order, results and
+  // the work counter
+  DBuf<EdgeDev> d_edges;
+  DBuf<int> d_eorder, d_efirst;
+  DBuf<unsigned> d_ecounter;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_check_ms = 0, last_plan_ms = 0;
   int64_t last_plan_launches = 0;
@@ -492,6 +498,7 @@ void smp_planner_destroy(smp_planner* p) {
   for (auto& q : p->qb) q.release();
   p->d_qdev.release(); p->d_counts.release(); p->d_lfin.release(); p->d_cq.release(); p->d_valid.release();
   p->d_ik_tasks.release(); p->d_ik_out.release(); p->d_ik_best.release(); p->d_path_edges.release();
+  p->d_edges.release(); p->d_eorder.release(); p->d_efirst.release(); p->d_ecounter.release();
   p->d_bricks.release(); p->d_d2.release(); p->d_d2b.release(); p->d_slab.release();
   p->d_keys.release(); p->d_sbits.release(); p->d_sdil.release(); p->d_scount.release(); p->d_sk01.release();
   if (p->d_rb) (void)hipFree(p->d_rb);
@@ -946,6 +953,187 @@ int smp_check_sequence(smp_planner* p, const double* q_rows, int64_t n, int chec
     if (!v[i]) { *first_invalid = i; break; }
   return SMP_OK;
 }
+
+// ------------------------------------------------------------------------------------------ dense edge checks
+// The density rule (include/smp_gpu.h, smp_check_edges): m hops of at most one planner step, the revolute and the
+// prismatic length each summed for joints ascending as stepTowardsRandSample does (birrt_star.cpp:5712-5868).  False
+// for a non-finite coordinate or more than SMP_EDGE_MAX_POINTS - 1 segments.
+static bool edge_density(const smp_planner* p, const double* a, const double* b, int* m_out) {
+  const int* rev = p->robot.dev.rev;
+  double sr = 0.0, sp = 0.0;
+  for (int j = 0; j < NJ; ++j) {
+    if (!std::isfinite(a[j]) || !std::isfinite(b[j])) return false;
+    const double d = b[j] - a[j];
+    if (rev[j]) sr += d * d; else sp += d * d;
+  }
+  const double lr = std::sqrt(sr), lp = std::sqrt(sp);
+  const double x = std::ceil(std::max(lr, lp) / p->params.step_factor);
+  if (!(x * p->params.num_traj_segments <= (double)(SMP_EDGE_MAX_POINTS - 1))) return false;
+  *m_out = x < 1.0 ? 1 : (int)x;
+  return true;
+}
+
+static bool make_edge(const smp_planner* p, const double* a, const double* b, EdgeDev* e) {
+  int m = 0;
+  if (!edge_density(p, a, b, &m)) return false;
+  for (int j = 0; j < NJ; ++j) { e->a[j] = a[j]; e->b[j] = b[j]; }
+  e->M = p->params.num_traj_segments * m;
+  e->pad = 0;
+  return true;
+}
+
+// One edges_kernel launch over the table: first[i] = first colliding point of edge i, -1 if it is free.  The
+// workgroups draw the edges longest first from a counter zeroed on the stream.
+static int run_edges(smp_planner* p, const std::vector<EdgeDev>& edges, int self, int map, std::vector<int>& first,
+                     double* kernel_ms) {
+  const size_t n = edges.size();
+  std::vector<int> order(n);
+  for (size_t i = 0; i < n; ++i) order[i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return edges[x].M > edges[y].M; });
+  first.assign(n, -1);
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(p->d_edges.reserve(n));
+  HIPCHK(p->d_eorder.reserve(n));
+  HIPCHK(p->d_efirst.reserve(n));
+  HIPCHK(p->d_ecounter.reserve(1));
+  HIPCHK(hipMemcpyAsync(p->d_edges.p, edges.data(), n * sizeof(EdgeDev), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemcpyAsync(p->d_eorder.p, order.data(), n * sizeof(int), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
+  const int grid = (int)std::min<size_t>(n, (size_t)p->num_cus);  // the tile's LDS admits one workgroup per CU
+  HIPCHK(hipEventRecord(p->ev0, p->stream));
+  launch_edges(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_edges.p, p->d_eorder.p, (int)n, self,
+               map && p->have_scene, p->d_ecounter.p, p->d_efirst.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(p->ev1, p->stream));
+  HIPCHK(hipMemcpyAsync(first.data(), p->d_efirst.p, n * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+  if (kernel_ms) *kernel_ms = ms;
+  return SMP_OK;
+}
+
+// Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule.
+int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, int check_self,
+                    int check_map, int64_t* first_invalid, int32_t* n_points) {
+  if (!p || n < 0 || (n > 0 && (!from_rows || !to_rows || !first_invalid))) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  if (n == 0) return SMP_OK;
+  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+  if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  std::vector<EdgeDev> edges((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    if (!make_edge(p, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
+  std::vector<int> first;
+  double ms = 0;
+  const int st = run_edges(p, edges, check_self, check_map, first, &ms);
+  if (st != SMP_OK) return st;
+  p->last_check_ms = ms;
+  for (int64_t i = 0; i < n; ++i) {
+    first_invalid[i] = first[(size_t)i];
+    if (n_points) n_points[i] = edges[(size_t)i].M + 1;
+  }
+  return SMP_OK;
+}
+
+// Path shortcutting: every candidate waypoint pair checked densely in one launch, then the cheapest route through the
+// valid pairs (host, fp64), with the via nodes of the chosen edges inserted.
+int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map, int window,
+                      double** out_waypoints, int64_t* n_out, smp_shortcut_info* info) {
+  if (!p || !waypoints || !out_waypoints || !n_out || k < 2) return SMP_ERR_ARG;
+  const auto t_begin = std::chrono::steady_clock::now();
+  *out_waypoints = nullptr;
+  *n_out = 0;
+  if (info) {
+    std::memset(info, 0, sizeof(*info));
+    info->first_blocked = -1;
+  }
+  if (int b_ = busy_check(p)) return b_;
+  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+  if (k > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  const int64_t w = (window <= 0 || window > k - 1) ? k - 1 : window;
+  // candidates (i, j), i < j <= i + w, in the order of the dynamic program: j ascending, then i ascending
+  const int64_t n_edges = w * (k - 1) - w * (w - 1) / 2;
+  if (n_edges > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  std::vector<EdgeDev> edges((size_t)n_edges);
+  {
+    size_t e = 0;
+    for (int64_t j = 1; j < k; ++j)
+      for (int64_t i = std::max<int64_t>(0, j - w); i < j; ++i, ++e)
+        if (!make_edge(p, waypoints + i * NJ, waypoints + j * NJ, &edges[e])) return SMP_ERR_ARG;
+  }
+  std::vector<int> first;
+  double ms = 0;
+  const int st = run_edges(p, edges, check_self, check_map, first, &ms);
+  if (st != SMP_OK) return st;
+  auto dist = [&](int64_t i, int64_t j) {  // DH:128-156
+    double s = 0.0;
+    for (int c = 0; c < NJ; ++c) {
+      const double d = waypoints[j * NJ + c] - waypoints[i * NJ + c];
+      s += d * d;
+    }
+    return std::sqrt(s);
+  };
+  std::vector<double> dp((size_t)k, HUGE_VAL);
+  std::vector<int64_t> pred((size_t)k, -1), pred_edge((size_t)k, -1);
+  dp[0] = 0.0;
+  int64_t n_valid = 0, checked = 0, first_blocked = -1;
+  double cost_in = 0.0;
+  {
+    size_t e = 0;
+    for (int64_t j = 1; j < k; ++j) {
+      cost_in += dist(j - 1, j);
+      for (int64_t i = std::max<int64_t>(0, j - w); i < j; ++i, ++e) {
+        const int f = first[e];
+        checked += f < 0 ? edges[e].M + 1 : f + 1;
+        if (f >= 0) {
+          if (i == j - 1 && first_blocked < 0) first_blocked = i;
+          continue;
+        }
+        ++n_valid;
+        const double c = dp[(size_t)i] + dist(i, j);
+        if (c < dp[(size_t)j]) { dp[(size_t)j] = c; pred[(size_t)j] = i; pred_edge[(size_t)j] = (int64_t)e; }
+      }
+    }
+  }
+  const bool reached = pred[(size_t)(k - 1)] >= 0;
+  int rc = SMP_ERR_NO_SOLUTION;
+  if (reached) {
+    std::vector<int64_t> route;  // edge indices, goal to start
+    for (int64_t j = k - 1; j > 0; j = pred[(size_t)j]) route.push_back(pred_edge[(size_t)j]);
+    const int nseg = p->params.num_traj_segments;
+    int64_t rows = 1;
+    for (int64_t e : route) rows += edges[(size_t)e].M / nseg;
+    double* out = static_cast<double*>(std::malloc((size_t)rows * NJ * sizeof(double)));
+    if (!out) return SMP_ERR_CAPACITY;
+    int64_t r = 0;
+    for (size_t t = route.size(); t-- > 0;) {
+      const EdgeDev& ed = edges[(size_t)route[t]];
+      double step[NJ];
+      for (int c = 0; c < NJ; ++c) step[c] = (ed.b[c] - ed.a[c]) / (double)ed.M;
+      for (int h = 0; h < ed.M; h += nseg, ++r)  // the start waypoint (h = 0), then the via nodes
+        for (int c = 0; c < NJ; ++c) out[r * NJ + c] = h == 0 ? ed.a[c] : ed.a[c] + (double)h * step[c];
+    }
+    for (int c = 0; c < NJ; ++c) out[r * NJ + c] = waypoints[(k - 1) * NJ + c];
+    *out_waypoints = out;
+    *n_out = rows;
+    rc = SMP_OK;
+  }
+  if (info) {
+    info->n_edges = n_edges;
+    info->n_valid = n_valid;
+    info->configs_checked = checked;
+    info->cost_in = cost_in;
+    info->cost_out = reached ? dp[(size_t)(k - 1)] : 0.0;
+    info->first_blocked = reached ? -1 : first_blocked;
+    info->kernel_ms = ms;
+    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  p->last_check_ms = ms;
+  return rc;
+}
+
+void smp_buffer_free(void* buffer) { std::free(buffer); }
 
 int smp_is_config_valid(smp_planner* p, const double q[8], int check_self, int check_map, int* valid) {
   if (!p || !q || !valid) return SMP_ERR_ARG;

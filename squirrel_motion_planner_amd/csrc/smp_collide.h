@@ -716,6 +716,16 @@ __device__ __forceinline__ bool sphere_prim(int ty, const double* __restrict__ h
 
 constexpr int NWAVE = BLOCK / 64;
 
+// Copies the robot model and the map configuration into LDS (read by every collision stage).
+__device__ __forceinline__ void stage_model(const RobotDev* rb, const MapCfg* mc, RobotDev* rbl, MapCfg* mcl) {
+  static_assert(sizeof(RobotDev) % 8 == 0 && sizeof(MapCfg) % 4 == 0, "staging granularity");
+  for (int i = threadIdx.x; i < (int)(sizeof(RobotDev) / 8); i += BLOCK)
+    reinterpret_cast<uint64_t*>(rbl)[i] = reinterpret_cast<const uint64_t*>(rb)[i];
+  for (int i = threadIdx.x; i < (int)(sizeof(MapCfg) / 4); i += BLOCK)
+    reinterpret_cast<uint32_t*>(mcl)[i] = reinterpret_cast<const uint32_t*>(mc)[i];
+  __syncthreads();
+}
+
 // LDS work area of one collision tile of CT configurations (CT a multiple of the wave count).
 template <int CT>
 struct TileLds {

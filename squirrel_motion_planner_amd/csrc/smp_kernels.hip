@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "smp_collide.h"
+#include "smp_edges.h"
 #include "smp_math.h"
 #include "smp_plan.h"
 #include "smp_types.h"
@@ -36,16 +37,6 @@ __shared__ MapCfg g_mc;
 // The per-lane constants of the job tiles (WideConst) of a workgroup that publishes jobs and runs a tile of its own now
 // and then (plan_kernel's leaders and scouts): filled once per launch, read back by job_tile_mask_out.
 __shared__ WideStash g_wk;
-
-// Copies the robot model and the map configuration into LDS (read by every collision stage).
-__device__ __forceinline__ void stage_model(const RobotDev* rb, const MapCfg* mc, RobotDev* rbl, MapCfg* mcl) {
-  static_assert(sizeof(RobotDev) % 8 == 0 && sizeof(MapCfg) % 4 == 0, "staging granularity");
-  for (int i = threadIdx.x; i < (int)(sizeof(RobotDev) / 8); i += BLOCK)
-    reinterpret_cast<uint64_t*>(rbl)[i] = reinterpret_cast<const uint64_t*>(rb)[i];
-  for (int i = threadIdx.x; i < (int)(sizeof(MapCfg) / 4); i += BLOCK)
-    reinterpret_cast<uint32_t*>(mcl)[i] = reinterpret_cast<const uint32_t*>(mc)[i];
-  __syncthreads();
-}
 
 template <int CT>
 __global__ void __launch_bounds__(BLOCK) check_kernel_t(const RobotDev* __restrict__ rb, SceneDev sc,
@@ -115,7 +106,8 @@ size_t check_kernels_private_bytes() {
                       reinterpret_cast<const void*>(&check_wide_kernel)};
   for (const void* k : ks)
     if (hipFuncGetAttributes(&fa, k) == hipSuccess && (size_t)fa.localSizeBytes > need) need = fa.localSizeBytes;
-  return need;
+  const size_t edges = edges_kernels_private_bytes();  // edges_kernel (smp_edges.hip) runs the same tiles
+  return edges > need ? edges : need;
 }
 
 void launch_check(int ct, int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const double* q,

@@ -4,8 +4,8 @@
 birrt_star_motion_planning::BiRRTstarPlanner (birrt_star.h:27-110) as the squirrel_8dof_planner node uses it
 (squirrel_8dof_planner.cpp:1221-1248): initialize, setOctree, setDisabledLinkMapCollisions,
 reset_planner_and_config, setPlanningSceneInfo, init_planner, run_planner, getJointTrajectoryRef,
-isConfigValid.  Every call lands in libsmp_gpu.so (HIP kernels on the GPU); nothing here computes planning
-or collision results on the CPU.
+isConfigValid, isEdgeValid (and shortcutTrajectory, a simplification pass the reference lacks).  Every call lands in
+libsmp_gpu.so (HIP kernels on the GPU); nothing here computes planning or collision results on the CPU.
 """
 import ctypes
 
@@ -279,6 +279,41 @@ class GpuPlanner:
                                        ctypes.byref(first)), "smp_check_sequence")
         return first.value
 
+    def check_edges(self, frm, to, check_self=True, check_map=True):
+        """Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule of smp_check_edges: (first_invalid,
+        n_points) per edge frm[i] -> to[i]; first_invalid is the index of the first colliding point, -1 if free."""
+        a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
+        b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
+        if len(a) != len(b):
+            raise ValueError("check_edges: %d start and %d end configurations" % (len(a), len(b)))
+        first = np.zeros(len(a), np.int64)
+        npts = np.zeros(len(a), np.int32)
+        check(lib().smp_check_edges(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(check_self),
+                                    int(check_map), first.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                    npts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "smp_check_edges")
+        return first, npts
+
+    def shortcut_path(self, path, check_self=True, check_map=True, window=0):
+        """smp_shortcut_path: every waypoint pair within `window` (0: all pairs) checked as a dense edge in one launch,
+        the cheapest route through the valid ones, via nodes inserted.  Returns (path (m, 8), info dict); a blocked
+        path raises SmpError with status SMP_ERR_NO_SOLUTION, its `info` attribute holding the dict."""
+        w = np.ascontiguousarray(np.asarray(path, np.float64).reshape(-1, 8))
+        out = _pd()
+        n_out = ctypes.c_int64()
+        info = L.ShortcutInfo()
+        rc = lib().smp_shortcut_path(self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map),
+                                     int(window), ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
+        d = {f: getattr(info, f) for f, _ in L.ShortcutInfo._fields_}
+        if rc != L.SMP_OK:
+            err = L.SmpError(rc, "smp_shortcut_path")
+            err.info = d
+            raise err
+        try:
+            res = np.ctypeslib.as_array(out, shape=(n_out.value, 8)).copy()
+        finally:
+            lib().smp_buffer_free(out)
+        return res, d
+
     def get_collisions(self, q):
         """getCollisions (birrt_star.cpp:6910-6914): (self pairs [(link a, link b)] in pair order, map-colliding links
         in name order) of one configuration, as link names; disabled links are listed too, as in the reference."""
@@ -545,6 +580,32 @@ class BiRRTstarPlanner:
 
     def isConfigValid(self, config, check_self_collision=True, check_map_collision=True):
         return bool(self._gpu.check_configs([config], check_self_collision, check_map_collision)[0])
+
+    def isEdgeValid(self, start_conf, end_conf, check_self_collision=True, check_map_collision=True):
+        """birrt_star.h:103-104 for the edge start_conf -> end_conf: (valid, last_valid_node_idx), the index as the
+        reference leaves it (birrt_star.cpp:6878-6895): the last point of a free edge, else the last free point before
+        the first colliding one (0 when the first point collides)."""
+        first, npts = self._gpu.check_edges([start_conf], [end_conf], check_self_collision, check_map_collision)
+        f = int(first[0])
+        return f < 0, (int(npts[0]) - 1 if f < 0 else max(f - 1, 0))
+
+    def shortcutTrajectory(self, trajectory, check_self_collision=True, check_map_collision=True, window=0):
+        """Shortens `trajectory` (a list of 8-value poses, e.g. getJointTrajectoryRef()) in place
+        (GpuPlanner.shortcut_path); False, trajectory untouched, when the path is blocked or has fewer than two poses.
+        The node would call it between getJointTrajectoryRef and normalizeTrajectory.  `shortcut_info` keeps the
+        call's counts, costs and timing."""
+        if len(trajectory) < 2:
+            return False
+        try:
+            path, self.shortcut_info = self._gpu.shortcut_path(trajectory, check_self_collision, check_map_collision,
+                                                               window)
+        except L.SmpError as e:
+            if e.status != L.SMP_ERR_NO_SOLUTION:
+                raise
+            self.shortcut_info = e.info
+            return False
+        trajectory[:] = [list(map(float, w)) for w in path]
+        return True
 
     def getCollisions(self, joint_positions, self_collisions, map_collisions):
         """birrt_star.cpp:6910-6914: appends to the two lists, as the reference does."""
