@@ -302,6 +302,43 @@ class BiRRTstarPlanner {
   // Counts, costs and timing of the last shortcutTrajectory.
   const smp_shortcut_info& lastShortcut() const { return shortcut_; }
 
+  // Repairs a trajectory in place (smp_repair_path): the stretches that fail the dense check (the planner's own paths
+  // can, and the scene may have changed since planning) are gathered into gaps between valid poses and each is bridged
+  // by the cheapest free one-via detour of `samples` per round, the sampling half width doubling over `rounds`; the via
+  // nodes of every edge are inserted, so consecutive poses stay at most one planner step apart.  The node calls it
+  // between getJointTrajectoryRef and shortcutTrajectory.  False, trajectory untouched, when a stretch stays blocked,
+  // an end pose is invalid or there are fewer than two poses.
+  bool repairTrajectory(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
+                        int samples = 256, int rounds = 4, unsigned long long seed = 1) {
+    need();
+    if (trajectory.size() < 2) return false;
+    vector<double> rows;
+    rows.reserve(trajectory.size() * 8);
+    for (size_t i = 0; i < trajectory.size(); ++i) {
+      if (trajectory[i].size() != 8) return false;
+      rows.insert(rows.end(), trajectory[i].begin(), trajectory[i].end());
+    }
+    smp_repair_opts o;
+    smp_repair_opts_default(&o);
+    o.samples = samples;
+    o.rounds = rounds;
+    o.seed = seed;
+    double* out = nullptr;
+    int64_t n_out = 0;
+    const int st = smp_repair_path(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
+                                   check_map_collision, &o, &out, &n_out, &repair_);
+    if (st == SMP_ERR_NO_SOLUTION || st == SMP_ERR_START_INVALID || st == SMP_ERR_GOAL_INVALID) return false;
+    check(st, "repairTrajectory");
+    vector<vector<double> > res((size_t)n_out, vector<double>(8));
+    for (int64_t i = 0; i < n_out; ++i)
+      for (int j = 0; j < 8; ++j) res[(size_t)i][(size_t)j] = out[i * 8 + j];
+    smp_buffer_free(out);
+    trajectory.swap(res);
+    return true;
+  }
+  // Counts, costs and timing of the last repairTrajectory.
+  const smp_repair_info& lastRepair() const { return repair_; }
+
   // birrt_star.cpp:6910-6914 (collision_checker.hpp:123-132, 594-630): appends the colliding self pairs (pair order)
   // and the map-colliding links (name order, disabled links included) of one configuration.
   void getCollisions(const std::vector<double>& jointPositions, std::vector<std::pair<std::string, std::string> >& selfCollisions,
@@ -395,6 +432,7 @@ class BiRRTstarPlanner {
   smp_params params_;
   smp_stats stats_{};
   smp_shortcut_info shortcut_{};
+  smp_repair_info repair_{};
   double env_x_[2] = {0, 0}, env_y_[2] = {0, 0};
   vector<double> start_, goal_;
   bool self_ = true, map_ = true, ready_ = false;

@@ -43,7 +43,11 @@
  *   smp_shortcut_path          a simplification pass over a finished path (the reference has none: the node resamples
  *                              getJointTrajectoryRef as it is, squirrel_8dof_planner.cpp:1238-1248): every waypoint
  *                              pair as one dense edge check, then the cheapest route (edge cost as DH:128-156)
- *   smp_buffer_free            releases smp_shortcut_path's output
+ *   smp_sample_detours         one-via detours a -> v -> b for a table of gaps: samples drawn and both legs checked
+ *                              densely on the device, one launch (the reference has no counterpart)
+ *   smp_repair_path            a repair pass over a path that fails the dense check: blocked stretches gathered into
+ *                              gaps between valid waypoints, each bridged by the cheapest free detour
+ *   smp_buffer_free            releases smp_shortcut_path's and smp_repair_path's output
  *   smp_normalize_trajectory   Planner::normalizeTrajectory (squirrel_8dof_planner.cpp:1557-1637), host only
  *   smp_ik_solve               BiRRTstarPlanner::getFullPoseFromEEPose (birrt_star.cpp:1627-1686) ->
  *                              RobotController::run_VDLS_Control_Connector (control_laws.cpp:3283-3712):
@@ -347,6 +351,55 @@ typedef struct smp_shortcut_info {   /* may be NULL */
 int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map, int window,
                       double** out_waypoints, int64_t* n_out, smp_shortcut_info* info);
 void smp_buffer_free(void* buffer);  /* NULL is allowed */
+
+/* Path repair: one-via detours around the blocked stretches of a path (the planner's own full paths can fail the dense
+ * check, and the scene can change between planning and execution; smp_shortcut_path then only answers "blocked").
+ *
+ * One detour item (gap g, sample s) of a round: with the gap's anchors a and b, the half width h, the arm's joint limits
+ * q_min / q_max and the planner's Philox draw u01 (seed, query = g, iteration = round, outer = s, inner = 0, index = j),
+ *   c[j] = 0.5 * (a[j] + b[j]);  t = 2.0 * u01 - 1.0;  v[j] = c[j] + t * h;  v[j] clamped to [q_min[j], q_max[j]] for
+ *   j >= 2 (x and y are not clamped: environment bounds belong to a query), every operation rounded on its own.
+ * The legs a -> v and v -> b are edges of the density rule above (M1 and M2 segments, formed on the device); the item is
+ * free if every point of both legs is.  A leg of more than SMP_EDGE_MAX_POINTS points makes the item blocked and is
+ * reported with 0 segments. */
+typedef struct smp_detour { double v[8]; int32_t M1, M2; int32_t free; int32_t pad; } smp_detour;
+/* n_gaps pairs from_rows[g] -> to_rows[g]; out[g * samples + s]. One launch.  g in the Philox stream is the row index.
+ * Honours smp_set_disabled_map_links.  n_gaps = 0: SMP_OK.  samples < 1, a non-finite coordinate or half width:
+ * SMP_ERR_ARG.  check_map without a scene: SMP_ERR_ARG.  n_gaps * samples > SMP_EDGE_TABLE_MAX: SMP_ERR_CAPACITY. */
+int smp_sample_detours(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps,
+                       int samples, double half_width, uint64_t seed, uint32_t round,
+                       int check_self, int check_map, smp_detour* out);
+
+typedef struct smp_repair_opts { int samples; int rounds; uint64_t seed; } smp_repair_opts;  /* NULL: defaults */
+void smp_repair_opts_default(smp_repair_opts*);   /* samples 256, rounds 4, seed 1 */
+typedef struct smp_repair_info {   /* may be NULL */
+  int64_t n_blocked_edges, n_gaps, n_repaired, n_items, n_free;  /* blocked adjacent edges; gaps, of which closed;
+                                                                     detour items checked over all rounds, of which free */
+  int32_t rounds_used;      /* detour launches made (0 without a gap) */
+  double cost_in, cost_out; /* sums of dist, i ascending, over the input rows / the route's rows (via nodes excluded);
+                               cost_out is 0 when gaps stay open */
+  int64_t first_blocked;    /* gaps stay open: the smallest blocked edge index of the first open gap; else -1 */
+  double kernel_ms, total_ms;  /* HIP events around the check, edge and detour kernels; host clock, entry to return */
+} smp_repair_info;
+/* Repairs a path of k waypoints (row-major k x 8).
+ *  1. Validity: the k waypoints through the batch checker (smp_check_configs), the k - 1 adjacent edges through the edge
+ *     kernel (smp_check_edges).  w_0 invalid: SMP_ERR_START_INVALID; w_k-1 invalid: SMP_ERR_GOAL_INVALID.
+ *  2. Gaps: for every blocked adjacent edge i, ascending, l = the largest index <= i whose waypoint is valid, r = the
+ *     smallest index >= i + 1 whose waypoint is valid; gaps whose index ranges overlap (l' < r) are merged, so the gaps
+ *     are disjoint and ordered.  Without a blocked edge the output is the input route with via nodes inserted.
+ *  3. Rounds rho = 0 .. rounds - 1: one launch of detour items over the gaps still open (anchors w_l, w_r, g = the gap's
+ *     index among all gaps, round = rho, h = step_factor * 2^rho).  Per gap the chosen sample is the first strict minimum,
+ *     s ascending, of dist(a, v) + dist(v, b) over the free items (dist as in smp_shortcut_path, formed on the host from
+ *     the returned v); a gap with a chosen sample is closed.
+ *  4. Gaps open after the last round: SMP_ERR_NO_SOLUTION, info->first_blocked set, *out_waypoints = NULL, *n_out = 0.
+ *  5. Output: the route w_0 ... w_l, v, w_r, ... (waypoints strictly inside a gap dropped) with the via nodes of every
+ *     route edge between its rows, as smp_shortcut_path writes them: every row was collision-checked and every hop is at
+ *     most one planner step.  Release *out_waypoints with smp_buffer_free.
+ * k < 2, a non-finite coordinate, an edge of more than SMP_EDGE_MAX_POINTS points, samples < 1, rounds < 1 (or more than
+ * 32): SMP_ERR_ARG.  check_map without a scene: SMP_ERR_ARG.  k or n_gaps * samples > SMP_EDGE_TABLE_MAX:
+ * SMP_ERR_CAPACITY. */
+int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                    const smp_repair_opts* opts, double** out_waypoints, int64_t* n_out, smp_repair_info* info);
 
 /* n poses of `dim` values, row-major.  *n_out = rows of the normalized trajectory; with out == NULL only counts,
  * else writes them (SMP_ERR_CAPACITY if out_cap < *n_out).  For dim < 1 or n <= 1 the reference leaves its output

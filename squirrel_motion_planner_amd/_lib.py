@@ -99,6 +99,24 @@ class ShortcutInfo(ctypes.Structure):
                 ("first_blocked", _i64), ("kernel_ms", _d), ("total_ms", _d)]
 
 
+class Detour(ctypes.Structure):
+    """smp_detour: one item (gap, sample) of smp_sample_detours."""
+    _fields_ = [("v", _d * 8), ("M1", ctypes.c_int32), ("M2", ctypes.c_int32), ("free", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+class RepairOpts(ctypes.Structure):
+    """smp_repair_opts: samples per gap and round, rounds, Philox seed."""
+    _fields_ = [("samples", _i), ("rounds", _i), ("seed", ctypes.c_uint64)]
+
+
+class RepairInfo(ctypes.Structure):
+    """smp_repair_info: counts, costs and timing of one smp_repair_path call."""
+    _fields_ = [("n_blocked_edges", _i64), ("n_gaps", _i64), ("n_repaired", _i64), ("n_items", _i64), ("n_free", _i64),
+                ("rounds_used", ctypes.c_int32), ("cost_in", _d), ("cost_out", _d), ("first_blocked", _i64),
+                ("kernel_ms", _d), ("total_ms", _d)]
+
+
 SMP_EDGE_MAX_POINTS = 1 << 20
 SMP_EDGE_TABLE_MAX = 1 << 20
 
@@ -148,6 +166,11 @@ EXPORTS = [
     ("smp_check_edges", _i, [_p, _pd, _pd, _i64, _i, _i, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_int32)]),
     ("smp_shortcut_path", _i, [_p, _pd, _i64, _i, _i, _i, ctypes.POINTER(_pd), ctypes.POINTER(_i64),
                                ctypes.POINTER(ShortcutInfo)]),
+    ("smp_sample_detours", _i, [_p, _pd, _pd, _i64, _i, _d, ctypes.c_uint64, ctypes.c_uint32, _i, _i,
+                                ctypes.POINTER(Detour)]),
+    ("smp_repair_opts_default", None, [ctypes.POINTER(RepairOpts)]),
+    ("smp_repair_path", _i, [_p, _pd, _i64, _i, _i, ctypes.POINTER(RepairOpts), ctypes.POINTER(_pd),
+                             ctypes.POINTER(_i64), ctypes.POINTER(RepairInfo)]),
     ("smp_buffer_free", None, [_p]),
     ("smp_normalize_trajectory", _i, [_pd, _i64, _i, _pd, _pd, _i64, ctypes.POINTER(_i64)]),
     ("smp_ik_solve", _i, [_p, ctypes.POINTER(IkRequest), _i, ctypes.POINTER(IkResult)]),

@@ -21,6 +21,7 @@
 #include "smp_ik.h"
 #include "smp_math.h"
 #include "smp_plan.h"
+#include "smp_repair.h"
 #include "smp_scene.h"
 #include "smp_types.h"
 
@@ -149,6 +150,10 @@ struct smp_planner {
   DBuf<EdgeDev> d_edges;
   DBuf<int> d_eorder, d_efirst;
   DBuf<unsigned> d_ecounter;
+  // batched one-via detours (smp_sample_detours / smp_repair_path): gap table and per-item results; the work counter
+  // is d_ecounter
+  DBuf<GapDev> d_gaps;
+  DBuf<DetourDev> d_detours;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_check_ms = 0, last_plan_ms = 0;
   int64_t last_plan_launches = 0;
@@ -448,6 +453,7 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
     need = std::max(need, check_kernels_private_bytes());
     need = std::max(need, ik_kernels_private_bytes());
     need = std::max(need, scene_kernels_private_bytes());
+    need = std::max(need, repair_kernels_private_bytes());
     size_t cur = 0;
     if (hipDeviceGetLimit(&cur, hipLimitStackSize) == hipSuccess && cur < need) {
       need = (need + 255) / 256 * 256;
@@ -499,6 +505,7 @@ void smp_planner_destroy(smp_planner* p) {
   p->d_qdev.release(); p->d_counts.release(); p->d_lfin.release(); p->d_cq.release(); p->d_valid.release();
   p->d_ik_tasks.release(); p->d_ik_out.release(); p->d_ik_best.release(); p->d_path_edges.release();
   p->d_edges.release(); p->d_eorder.release(); p->d_efirst.release(); p->d_ecounter.release();
+  p->d_gaps.release(); p->d_detours.release();
   p->d_bricks.release(); p->d_d2.release(); p->d_d2b.release(); p->d_slab.release();
   p->d_keys.release(); p->d_sbits.release(); p->d_sdil.release(); p->d_scount.release(); p->d_sk01.release();
   if (p->d_rb) (void)hipFree(p->d_rb);
@@ -1130,6 +1137,261 @@ int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int ch
     info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   p->last_check_ms = ms;
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------ path repair
+static_assert(sizeof(smp_detour) == sizeof(DetourDev), "smp_detour is the kernel's record");
+
+// One detours_kernel launch: out[g * samples + s] for the gaps of the table, items drawn from a counter zeroed on the
+// stream.
+static int run_detours(smp_planner* p, const std::vector<GapDev>& gaps, int samples, double h, uint64_t seed,
+                       uint32_t round, int self, int map, DetourDev* out, double* kernel_ms) {
+  const size_t n_items = gaps.size() * (size_t)samples;
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(p->d_gaps.reserve(gaps.size()));
+  HIPCHK(p->d_detours.reserve(n_items));
+  HIPCHK(p->d_ecounter.reserve(1));
+  HIPCHK(hipMemcpyAsync(p->d_gaps.p, gaps.data(), gaps.size() * sizeof(GapDev), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
+  DetourArgs a;
+  a.n_items = (int)n_items;
+  a.samples = samples;
+  a.n_seg = p->params.num_traj_segments;
+  a.max_points = SMP_EDGE_MAX_POINTS;
+  a.self = self;
+  a.map = map && p->have_scene;
+  a.round = round;
+  a.seed = seed;
+  a.step = p->params.step_factor;
+  a.h = h;
+  const int grid = (int)std::min<size_t>(n_items, (size_t)p->num_cus);  // the tile's LDS admits one workgroup per CU
+  HIPCHK(hipEventRecord(p->ev0, p->stream));
+  launch_detours(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_gaps.p, a, p->d_ecounter.p, p->d_detours.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(p->ev1, p->stream));
+  HIPCHK(hipMemcpyAsync(out, p->d_detours.p, n_items * sizeof(DetourDev), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+  if (kernel_ms) *kernel_ms = ms;
+  return SMP_OK;
+}
+
+static bool finite_rows(const double* rows, int64_t n) {
+  for (int64_t i = 0; i < n * NJ; ++i)
+    if (!std::isfinite(rows[i])) return false;
+  return true;
+}
+
+int smp_sample_detours(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps, int samples,
+                       double half_width, uint64_t seed, uint32_t round, int check_self, int check_map,
+                       smp_detour* out) {
+  if (!p || n_gaps < 0 || samples < 1 || !std::isfinite(half_width) || (n_gaps > 0 && (!from_rows || !to_rows || !out)))
+    return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  if (n_gaps == 0) return SMP_OK;
+  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+  if (n_gaps > SMP_EDGE_TABLE_MAX || n_gaps * (int64_t)samples > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  if (!finite_rows(from_rows, n_gaps) || !finite_rows(to_rows, n_gaps)) return SMP_ERR_ARG;
+  std::vector<GapDev> gaps((size_t)n_gaps);
+  for (int64_t g = 0; g < n_gaps; ++g) {
+    for (int j = 0; j < NJ; ++j) {
+      gaps[(size_t)g].a[j] = from_rows[g * NJ + j];
+      gaps[(size_t)g].b[j] = to_rows[g * NJ + j];
+    }
+    gaps[(size_t)g].g = (unsigned)g;
+    gaps[(size_t)g].pad = 0;
+  }
+  double ms = 0;
+  const int st = run_detours(p, gaps, samples, half_width, seed, round, check_self, check_map,
+                             reinterpret_cast<DetourDev*>(out), &ms);
+  if (st != SMP_OK) return st;
+  p->last_check_ms = ms;
+  return SMP_OK;
+}
+
+void smp_repair_opts_default(smp_repair_opts* o) {
+  if (!o) return;
+  o->samples = 256;
+  o->rounds = 4;
+  o->seed = 1;
+}
+
+// Path repair: the waypoints and the adjacent edges checked, the blocked stretches gathered into gaps between valid
+// waypoints, and each gap bridged by the cheapest free one-via detour of the first round that has one.
+int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                    const smp_repair_opts* opts, double** out_waypoints, int64_t* n_out, smp_repair_info* info) {
+  if (!p || !waypoints || !out_waypoints || !n_out || k < 2) return SMP_ERR_ARG;
+  const auto t_begin = std::chrono::steady_clock::now();
+  *out_waypoints = nullptr;
+  *n_out = 0;
+  if (info) {
+    std::memset(info, 0, sizeof(*info));
+    info->first_blocked = -1;
+  }
+  smp_repair_opts o;
+  smp_repair_opts_default(&o);
+  if (opts) o = *opts;
+  if (o.samples < 1 || o.rounds < 1 || o.rounds > 32) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+  if (k > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  if (!finite_rows(waypoints, k)) return SMP_ERR_ARG;
+  auto W = [&](int64_t i) { return waypoints + i * NJ; };
+  auto dist = [](const double* a, const double* b) {  // DH:128-156
+    double s = 0.0;
+    for (int c = 0; c < NJ; ++c) {
+      const double d = b[c] - a[c];
+      s += d * d;
+    }
+    return std::sqrt(s);
+  };
+  double kernel_ms = 0, ms = 0;
+  // 1. validity of the waypoints and of the adjacent edges
+  std::vector<uint8_t> valid((size_t)k);
+  {
+    std::vector<double> soa((size_t)k * NJ);
+    for (int64_t i = 0; i < k; ++i)
+      for (int j = 0; j < NJ; ++j) soa[(size_t)j * k + i] = W(i)[j];
+    const int st = smp_check_configs(p, soa.data(), k, check_self, check_map, valid.data());
+    if (st != SMP_OK) return st;
+    kernel_ms += p->last_check_ms;
+  }
+  if (!valid[0]) return SMP_ERR_START_INVALID;
+  if (!valid[(size_t)(k - 1)]) return SMP_ERR_GOAL_INVALID;
+  std::vector<EdgeDev> edges((size_t)(k - 1));
+  for (int64_t i = 0; i + 1 < k; ++i)
+    if (!make_edge(p, W(i), W(i + 1), &edges[(size_t)i])) return SMP_ERR_ARG;
+  std::vector<int> first;
+  {
+    const int st = run_edges(p, edges, check_self, check_map, first, &ms);
+    if (st != SMP_OK) return st;
+    kernel_ms += ms;
+  }
+  // 2. gaps: (l, r) waypoint indices of the anchors, e = the gap's smallest blocked edge
+  struct Gap { int64_t l, r, e; bool open; double v[NJ]; };
+  std::vector<Gap> gaps;
+  int64_t n_blocked = 0;
+  double cost_in = 0.0;
+  for (int64_t i = 0; i + 1 < k; ++i) {
+    cost_in += dist(W(i), W(i + 1));
+    if (first[(size_t)i] < 0) continue;
+    ++n_blocked;
+    int64_t l = i, r = i + 1;
+    while (!valid[(size_t)l]) --l;  // w_0 and w_k-1 are valid
+    while (!valid[(size_t)r]) ++r;
+    if (!gaps.empty() && l < gaps.back().r) {
+      gaps.back().r = std::max(gaps.back().r, r);
+    } else {
+      Gap g{};
+      g.l = l; g.r = r; g.e = i; g.open = true;
+      gaps.push_back(g);
+    }
+  }
+  const int64_t n_gaps = (int64_t)gaps.size();
+  if (n_gaps * (int64_t)o.samples > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  // 3. rounds over the gaps still open
+  int64_t n_items = 0, n_free = 0, n_open = n_gaps;
+  int rounds_used = 0;
+  std::vector<GapDev> table;
+  std::vector<DetourDev> items;
+  for (int rho = 0; rho < o.rounds && n_open > 0; ++rho) {
+    table.clear();
+    for (int64_t g = 0; g < n_gaps; ++g) {
+      if (!gaps[(size_t)g].open) continue;
+      GapDev d;
+      for (int j = 0; j < NJ; ++j) {
+        d.a[j] = W(gaps[(size_t)g].l)[j];
+        d.b[j] = W(gaps[(size_t)g].r)[j];
+      }
+      d.g = (unsigned)g;
+      d.pad = 0;
+      table.push_back(d);
+    }
+    items.resize(table.size() * (size_t)o.samples);
+    const double h = std::ldexp(p->params.step_factor, rho);
+    const int st = run_detours(p, table, o.samples, h, o.seed, (uint32_t)rho, check_self, check_map, items.data(), &ms);
+    if (st != SMP_OK) return st;
+    kernel_ms += ms;
+    ++rounds_used;
+    n_items += (int64_t)items.size();
+    for (size_t t = 0; t < table.size(); ++t) {
+      Gap& g = gaps[table[t].g];
+      double best = HUGE_VAL;
+      int chosen = -1;
+      for (int s = 0; s < o.samples; ++s) {
+        const DetourDev& it = items[t * (size_t)o.samples + (size_t)s];
+        if (!it.free) continue;
+        ++n_free;
+        const double c = dist(table[t].a, it.v) + dist(it.v, table[t].b);
+        if (c < best) { best = c; chosen = s; }
+      }
+      if (chosen >= 0) {
+        for (int j = 0; j < NJ; ++j) g.v[j] = items[t * (size_t)o.samples + (size_t)chosen].v[j];
+        g.open = false;
+        --n_open;
+      }
+    }
+  }
+  int rc = SMP_OK;
+  int64_t first_blocked = -1;
+  double cost_out = 0.0;
+  if (n_open > 0) {
+    rc = SMP_ERR_NO_SOLUTION;  // 4.
+    for (const Gap& g : gaps)
+      if (g.open) { first_blocked = g.e; break; }
+  } else {
+    // 5. the route's rows, then the via nodes of every route edge between them
+    std::vector<const double*> route;
+    {
+      size_t g = 0;
+      for (int64_t i = 0; i < k;) {
+        route.push_back(W(i));
+        if (g < gaps.size() && gaps[g].l == i) {
+          route.push_back(gaps[g].v);
+          i = gaps[g].r;
+          ++g;
+        } else {
+          ++i;
+        }
+      }
+    }
+    const int nseg = p->params.num_traj_segments;
+    std::vector<EdgeDev> re(route.size() - 1);
+    int64_t rows = 1;
+    for (size_t t = 0; t + 1 < route.size(); ++t) {
+      if (!make_edge(p, route[t], route[t + 1], &re[t])) return SMP_ERR_ARG;
+      rows += re[t].M / nseg;
+      cost_out += dist(route[t], route[t + 1]);
+    }
+    double* out = static_cast<double*>(std::malloc((size_t)rows * NJ * sizeof(double)));
+    if (!out) return SMP_ERR_CAPACITY;
+    int64_t r = 0;
+    for (const EdgeDev& ed : re) {
+      double step[NJ];
+      for (int c = 0; c < NJ; ++c) step[c] = (ed.b[c] - ed.a[c]) / (double)ed.M;
+      for (int h = 0; h < ed.M; h += nseg, ++r)  // the edge's start (h = 0), then its via nodes
+        for (int c = 0; c < NJ; ++c) out[r * NJ + c] = h == 0 ? ed.a[c] : ed.a[c] + (double)h * step[c];
+    }
+    for (int c = 0; c < NJ; ++c) out[r * NJ + c] = W(k - 1)[c];
+    *out_waypoints = out;
+    *n_out = rows;
+  }
+  if (info) {
+    info->n_blocked_edges = n_blocked;
+    info->n_gaps = n_gaps;
+    info->n_repaired = n_gaps - n_open;
+    info->n_items = n_items;
+    info->n_free = n_free;
+    info->rounds_used = rounds_used;
+    info->cost_in = cost_in;
+    info->cost_out = cost_out;
+    info->first_blocked = first_blocked;
+    info->kernel_ms = kernel_ms;
+    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  p->last_check_ms = kernel_ms;
   return rc;
 }
 

@@ -314,6 +314,48 @@ class GpuPlanner:
             lib().smp_buffer_free(out)
         return res, d
 
+    def sample_detours(self, frm, to, samples, half_width, seed=1, round=0, check_self=True, check_map=True):
+        """smp_sample_detours: for every gap frm[g] -> to[g], `samples` one-via detours drawn around the gap's centre
+        within `half_width` and both legs of each checked densely, one launch.  Returns a dict of v (G, S, 8), M1, M2
+        and free (G, S)."""
+        a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
+        b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
+        if len(a) != len(b):
+            raise ValueError("sample_detours: %d start and %d end configurations" % (len(a), len(b)))
+        n = len(a) * max(int(samples), 0)
+        out = (L.Detour * max(n, 1))()
+        check(lib().smp_sample_detours(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(samples),
+                                       float(half_width), int(seed), int(round), int(check_self), int(check_map), out),
+              "smp_sample_detours")
+        rec = np.frombuffer(out, dtype=np.dtype([("v", np.float64, 8), ("M1", np.int32), ("M2", np.int32),
+                                                 ("free", np.int32), ("pad", np.int32)]), count=n)
+        shape = (len(a), int(samples))
+        return dict(v=rec["v"].reshape(shape + (8,)).copy(), M1=rec["M1"].reshape(shape).copy(),
+                    M2=rec["M2"].reshape(shape).copy(), free=rec["free"].reshape(shape).copy())
+
+    def repair_path(self, path, check_self=True, check_map=True, samples=256, rounds=4, seed=1):
+        """smp_repair_path: the blocked stretches of `path` gathered into gaps between valid waypoints and each bridged
+        by the cheapest free one-via detour, the half width doubling per round.  Returns (path (m, 8), info dict) with
+        the via nodes of every edge inserted; gaps that stay open raise SmpError with status SMP_ERR_NO_SOLUTION, its
+        `info` attribute holding the dict (as every other failure does)."""
+        w = np.ascontiguousarray(np.asarray(path, np.float64).reshape(-1, 8))
+        out = _pd()
+        n_out = ctypes.c_int64()
+        info = L.RepairInfo()
+        opts = L.RepairOpts(int(samples), int(rounds), int(seed))
+        rc = lib().smp_repair_path(self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map),
+                                   ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
+        d = {f: getattr(info, f) for f, _ in L.RepairInfo._fields_}
+        if rc != L.SMP_OK:
+            err = L.SmpError(rc, "smp_repair_path")
+            err.info = d
+            raise err
+        try:
+            res = np.ctypeslib.as_array(out, shape=(n_out.value, 8)).copy()
+        finally:
+            lib().smp_buffer_free(out)
+        return res, d
+
     def get_collisions(self, q):
         """getCollisions (birrt_star.cpp:6910-6914): (self pairs [(link a, link b)] in pair order, map-colliding links
         in name order) of one configuration, as link names; disabled links are listed too, as in the reference."""
@@ -603,6 +645,26 @@ class BiRRTstarPlanner:
             if e.status != L.SMP_ERR_NO_SOLUTION:
                 raise
             self.shortcut_info = e.info
+            return False
+        trajectory[:] = [list(map(float, w)) for w in path]
+        return True
+
+    def repairTrajectory(self, trajectory, check_self_collision=True, check_map_collision=True, samples=256,
+                         rounds=4, seed=1):
+        """Repairs `trajectory` (a list of 8-value poses, e.g. getJointTrajectoryRef()) in place
+        (GpuPlanner.repair_path): its blocked stretches are bridged by one-via detours and the via nodes of every edge
+        are inserted.  False, trajectory untouched, when a stretch stays blocked, an end pose is invalid or there are
+        fewer than two poses.  The node would call it between getJointTrajectoryRef and shortcutTrajectory.
+        `repair_info` keeps the call's counts, costs and timing."""
+        if len(trajectory) < 2:
+            return False
+        try:
+            path, self.repair_info = self._gpu.repair_path(trajectory, check_self_collision, check_map_collision,
+                                                           samples, rounds, seed)
+        except L.SmpError as e:
+            if e.status not in (L.SMP_ERR_NO_SOLUTION, L.SMP_ERR_START_INVALID, L.SMP_ERR_GOAL_INVALID):
+                raise
+            self.repair_info = e.info
             return False
         trajectory[:] = [list(map(float, w)) for w in path]
         return True
