@@ -1,8 +1,8 @@
 // Batched dense edge checks (gfx950): isEdgeValid (birrt_star.cpp:6864-6895) for a table of edges of very different
 // lengths, each interpolated at the planner's own collision density (DESIGN.md "Path shortcutting").
 //
-// The host forms every edge's point count (edge_density in smp_api.cpp: M = num_traj_segments * hops of at most one
-// planner step) and an order of the table, longest first; the kernel interpolates.  Point k of an edge a -> b is
+// The host forms every edge's point count (edge_density in smp_api_paths.cpp: M = num_traj_segments * hops of at most
+// one planner step) and an order of the table, longest first; the kernel interpolates.  Point k of an edge a -> b is
 // a[j] + k * ((b[j] - a[j]) / M) -- the quotient first, then the product, no contraction -- which for one hop is bit for
 // bit connect_nodes' trajectory (oracle/smp_oracle.cpp:511-516).
 //

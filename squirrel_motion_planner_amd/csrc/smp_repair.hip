@@ -21,7 +21,7 @@
 namespace smp {
 
 // Segments M = n * m of the leg whose squared revolute and prismatic lengths are sr and sp (the density rule, as
-// edge_density in smp_api.cpp); 0 for a leg of more than max_points points (or a non-finite length).
+// edge_density in smp_api_paths.cpp); 0 for a leg of more than max_points points (or a non-finite length).
 __device__ __forceinline__ int leg_segments(double sr, double sp, double step, int n_seg, int max_points) {
   const double x = ceil(fmax(sqrt(sr), sqrt(sp)) / step);
   if (!(x * n_seg <= (double)(max_points - 1))) return 0;
