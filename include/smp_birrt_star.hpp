@@ -339,6 +339,81 @@ class BiRRTstarPlanner {
   // Counts, costs and timing of the last repairTrajectory.
   const smp_repair_info& lastRepair() const { return repair_; }
 
+  // Clearance (not in the reference, whose getCollisions lists contacts only once they exist): how far a configuration
+  // or a dense edge is from the map and from self-collision, and which links are nearest (include/smp_gpu.h "Clearance
+  // queries").  Link fields are names, empty where there is none (map at max_dist; a part not asked for).
+  struct Clearance {
+    double map, self;                 // map: capped at max_dist, negative = penetration depth; self: uncapped
+    std::string map_link, self_a, self_b;
+  };
+  struct EdgeClearance {
+    double map, self;                 // the minima over the edge's points 0 .. n_points - 1
+    int map_point, self_point;        // the lowest point attaining each (-1: none)
+    std::string map_link, self_a, self_b;  // the witnesses of those points
+    int n_points;
+  };
+  struct TrajectoryClearance {
+    double map, self;                 // the minima over the trajectory's edges
+    int map_edge, map_point;          // the first edge attaining map and its point (-1: map is at max_dist)
+    int self_edge, self_point;
+    std::string map_link, self_a, self_b;
+    long long n_points;               // configurations evaluated
+  };
+  Clearance getClearance(const vector<double>& jointPositions, double max_dist = 0.3, bool check_self_collision = true,
+                         bool check_map_collision = true) {
+    need();
+    if (jointPositions.size() != 8) throw std::runtime_error("getClearance: 8 joint positions expected");
+    smp_clearance c;
+    check(smp_clearance_configs(planner_, jointPositions.data(), 1, max_dist, check_self_collision, check_map_collision,
+                                &c, nullptr), "getClearance");
+    Clearance o;
+    o.map = c.map; o.self = c.self;
+    o.map_link = link_name(c.map_link); o.self_a = link_name(c.self_a); o.self_b = link_name(c.self_b);
+    return o;
+  }
+  EdgeClearance getEdgeClearance(const vector<double>& start_conf, const vector<double>& end_conf, double max_dist = 0.3,
+                                 bool check_self_collision = true, bool check_map_collision = true) {
+    need();
+    if (start_conf.size() != 8 || end_conf.size() != 8) throw std::runtime_error("getEdgeClearance: 8 joint positions expected");
+    smp_edge_clearance c;
+    check(smp_clearance_edges(planner_, start_conf.data(), end_conf.data(), 1, max_dist, check_self_collision,
+                              check_map_collision, &c, nullptr), "getEdgeClearance");
+    EdgeClearance o;
+    o.map = c.map; o.self = c.self; o.map_point = c.map_point; o.self_point = c.self_point;
+    o.map_link = link_name(c.map_link); o.self_a = link_name(c.self_a); o.self_b = link_name(c.self_b);
+    o.n_points = c.n_points;
+    return o;
+  }
+  // The adjacent edges of the last planned trajectory (getJointTrajectoryRef) in one launch; false when it has fewer
+  // than two poses.  The first edge attaining each minimum is reported.
+  bool getTrajectoryClearance(TrajectoryClearance& out, double max_dist = 0.3, bool check_self_collision = true,
+                              bool check_map_collision = true) {
+    need();
+    if (traj_.size() < 2) return false;
+    const size_t ne = traj_.size() - 1;
+    vector<double> rows;
+    rows.reserve(traj_.size() * 8);
+    for (size_t i = 0; i < traj_.size(); ++i) rows.insert(rows.end(), traj_[i].begin(), traj_[i].end());
+    vector<smp_edge_clearance> e(ne);
+    check(smp_clearance_edges(planner_, rows.data(), rows.data() + 8, (int64_t)ne, max_dist, check_self_collision,
+                              check_map_collision, e.data(), nullptr), "getTrajectoryClearance");
+    size_t im = 0, is = 0;
+    long long pts = 0;
+    for (size_t i = 0; i < ne; ++i) {
+      if (e[i].map < e[im].map) im = i;
+      if (e[i].self < e[is].self) is = i;
+      pts += e[i].n_points;
+    }
+    out.map = e[im].map; out.self = e[is].self;
+    out.map_edge = e[im].map_point >= 0 ? (int)im : -1;
+    out.map_point = e[im].map_point;
+    out.self_edge = e[is].self_point >= 0 ? (int)is : -1;
+    out.self_point = e[is].self_point;
+    out.map_link = link_name(e[im].map_link); out.self_a = link_name(e[is].self_a); out.self_b = link_name(e[is].self_b);
+    out.n_points = pts;
+    return true;
+  }
+
   // birrt_star.cpp:6910-6914 (collision_checker.hpp:123-132, 594-630): appends the colliding self pairs (pair order)
   // and the map-colliding links (name order, disabled links included) of one configuration.
   void getCollisions(const std::vector<double>& jointPositions, std::vector<std::pair<std::string, std::string> >& selfCollisions,
@@ -415,6 +490,7 @@ class BiRRTstarPlanner {
   void need() const {
     if (!planner_) throw std::runtime_error("smp: BiRRTstarPlanner::initialize() not called");
   }
+  std::string link_name(int l) const { return l >= 0 ? std::string(smp_robot_link_name(robot_, l)) : std::string(); }
   void set_flag(int smp_params::*field, int v) {
     params_.*field = v;
     if (planner_) check(smp_planner_set_params(planner_, &params_), "smp_planner_set_params");

@@ -48,6 +48,11 @@
  *   smp_repair_path            a repair pass over a path that fails the dense check: blocked stretches gathered into
  *                              gaps between valid waypoints, each bridged by the cheapest free detour
  *   smp_buffer_free            releases smp_shortcut_path's and smp_repair_path's output
+ *   smp_clearance_configs      distance of a batch of configurations to the map and to self-collision, with the
+ *                              witness links, one launch (the reference has no counterpart: getCollisions lists
+ *                              contacts only once they exist)
+ *   smp_clearance_edges        the same along dense edges of the density rule: each edge's minima, the points and the
+ *                              links attaining them, one launch (the reference has no counterpart)
  *   smp_normalize_trajectory   Planner::normalizeTrajectory (squirrel_8dof_planner.cpp:1557-1637), host only
  *   smp_ik_solve               BiRRTstarPlanner::getFullPoseFromEEPose (birrt_star.cpp:1627-1686) ->
  *                              RobotController::run_VDLS_Control_Connector (control_laws.cpp:3283-3712):
@@ -400,6 +405,61 @@ typedef struct smp_repair_info {   /* may be NULL */
  * SMP_ERR_CAPACITY. */
 int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
                     const smp_repair_opts* opts, double** out_waypoints, int64_t* n_out, smp_repair_info* info);
+
+/* Clearance queries: how far a configuration is from the map and from self-collision, and which links are nearest.
+ * Every validity check above ends in a yes or no; these return the minimum behind it, with its witness.
+ *
+ * Definition, for a configuration q, a query distance D = max_dist and the planner's scene.  Body frames, sphere world
+ * centres wc and primitive world centres / x axes pw are the checker's (KDL Frame * Frame, Frame * Vector).  Every
+ * operation below is rounded on its own (no contraction), sums run left to right, and a minimum does not depend on the
+ * order of the sweep: ties are settled on link indices (smp_robot_link_name), never on item order.
+ *   gap(c, lo, hi) = c < lo ? lo - c : (c > hi ? c - hi : 0.0); cell (i, j, k) is the box lo = o + i * res,
+ *   hi = o + (i + 1) * res per axis.
+ *   Map term of sphere s (map-enabled link): min over the occupied cells of sqrt(gx*gx + gy*gy + gz*gz) - r_s, g the
+ *     gaps of wc_s to the cell; negative = penetration depth.  A centre whose cell floor((wc - o) / res) lies outside
+ *     the grid gives D (the boolean check takes such a sphere as free).
+ *   Map term of primitive p (upright; half height hz, centre (px, py, pz), x axis (c, s)): min over the occupied cells of
+ *     sqrt(dxy2 + dz*dz) with dz = max(zlo - (pz + hz), (pz - hz) - zhi, 0) and
+ *       cylinder (radius h0): dxy = max(sqrt(qx*qx + qy*qy) - h0, 0), qx = gap(px, xlo, xhi), qy = gap(py, ylo, yhi);
+ *         dxy2 = dxy*dxy;
+ *       box (half extents h0, h1): dxy2 = 0 if none of the cell test's four separating-axis comparisons holds
+ *         (|dx| > hw + (|c|*h0 + |s|*h1), |dy| > hw + (|s|*h0 + |c|*h1), |c*dx + s*dy| > h0 + hw*(|c| + |s|),
+ *         |c*dy - s*dx| > h1 + hw*(|c| + |s|); hw = 0.5*res, dx = 0.5*(xlo + xhi) - px, dy likewise); else the least of
+ *         eight squared distances: each corner (X, Y) of the cell's square to the solid rectangle, ex = X - px,
+ *         ey = Y - py, lx = |c*ex + s*ey|, ly = |c*ey - s*ex|, qx = max(lx - h0, 0), qy = max(ly - h1, 0),
+ *         qx*qx + qy*qy; and each corner ((px + sx*(c*h0)) - sy*(s*h1), (py + sx*(s*h0)) + sy*(c*h1)), sx, sy = +-1, of
+ *         the rectangle to the square, gx*gx + gy*gy of its gaps.  (Two disjoint convex polygons attain their distance
+ *         at a vertex of one of them.)
+ *     A primitive overlapping a cell has term 0: primitives have no penetration depth.  A centre column outside the grid
+ *     gives D.
+ *   map = min(D, all map terms); map_link = the link of a term equal to it, the smallest link index among several,
+ *     -1 when map == D.
+ *   self = min over the model's self pairs (the flat lists of every validity check: sphere pairs and (primitive, sphere)
+ *     pairs of the enabled, non-rigid link pairs) of
+ *       sphere pair (a, b): sqrt(ex*ex + ey*ey + ez*ez) - (r_a + r_b), e = wc_a - wc_b;
+ *       (primitive, sphere): sqrt(q2) - r_s, q2 the squared distance of the sphere's centre to the solid primitive as
+ *         the validity check forms it (box: qx*qx + qy*qy + qz*qz; cylinder: qr*qr + qz*qz);
+ *     uncapped.  self_a < self_b are the link indices of a pair attaining it, the lexicographically smallest (a, b)
+ *     among equal minima.
+ * sqrt is monotone and sqrt(fl(r * r)) == r, so a term > 0 means the boolean test of that item is free and a term < 0
+ * that it collides; map == 0 arises from a primitive overlapping a cell and means colliding.
+ * An edge is the points 0..M of the density rule (smp_check_edges): map and self are the minima over its points,
+ * map_point / self_point the lowest point index attaining each (map_point = -1 when map == D), and the link fields are
+ * those of that point. */
+typedef struct smp_clearance { double map, self; int32_t map_link, self_a, self_b, pad; } smp_clearance;            /* 32 B */
+typedef struct smp_edge_clearance { double map, self; int32_t map_point, self_point, map_link, self_a, self_b, n_points; } smp_edge_clearance;  /* 40 B */
+typedef struct smp_clearance_info { int64_t n_points; double kernel_ms, total_ms; } smp_clearance_info;             /* may be NULL */
+/* n configurations (row-major n x 8), resp. n edges from_rows[i] -> to_rows[i]; one kernel launch each.  Both honour
+ * smp_set_disabled_map_links.  A part not asked for reports map = max_dist, map_link = -1, resp. self = +inf,
+ * self_a = self_b = -1 (and the point fields -1).  info->n_points: configurations evaluated (for edges the sum of
+ * M + 1).  n = 0: SMP_OK.  SMP_ERR_ARG: a NULL planner or output, a non-finite coordinate, max_dist not finite or
+ * <= 0, a max_dist whose largest prefilter threshold floor(((r + max_dist + 1e-6) / res)^2) reaches the clamp of the
+ * box-gap field (65535; about 12.5 m at 5 cm), an edge of more than SMP_EDGE_MAX_POINTS points, with_map without a
+ * scene (as smp_check_edges).  n > SMP_EDGE_TABLE_MAX: SMP_ERR_CAPACITY. */
+int smp_clearance_configs(smp_planner* p, const double* q_rows, int64_t n, double max_dist, int with_self, int with_map,
+                          smp_clearance* out, smp_clearance_info* info);
+int smp_clearance_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, double max_dist,
+                        int with_self, int with_map, smp_edge_clearance* out, smp_clearance_info* info);
 
 /* n poses of `dim` values, row-major.  *n_out = rows of the normalized trajectory; with out == NULL only counts,
  * else writes them (SMP_ERR_CAPACITY if out_cap < *n_out).  For dim < 1 or n <= 1 the reference leaves its output

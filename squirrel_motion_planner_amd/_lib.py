@@ -117,6 +117,24 @@ class RepairInfo(ctypes.Structure):
                 ("kernel_ms", _d), ("total_ms", _d)]
 
 
+class Clearance(ctypes.Structure):
+    """smp_clearance: map and self clearance of one configuration with the witness links."""
+    _fields_ = [("map", _d), ("self", _d), ("map_link", ctypes.c_int32), ("self_a", ctypes.c_int32),
+                ("self_b", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class EdgeClearance(ctypes.Structure):
+    """smp_edge_clearance: the minima over a dense edge, the points and links attaining them."""
+    _fields_ = [("map", _d), ("self", _d), ("map_point", ctypes.c_int32), ("self_point", ctypes.c_int32),
+                ("map_link", ctypes.c_int32), ("self_a", ctypes.c_int32), ("self_b", ctypes.c_int32),
+                ("n_points", ctypes.c_int32)]
+
+
+class ClearanceInfo(ctypes.Structure):
+    """smp_clearance_info: configurations evaluated and timing of one clearance call."""
+    _fields_ = [("n_points", _i64), ("kernel_ms", _d), ("total_ms", _d)]
+
+
 SMP_EDGE_MAX_POINTS = 1 << 20
 SMP_EDGE_TABLE_MAX = 1 << 20
 
@@ -172,6 +190,10 @@ EXPORTS = [
     ("smp_repair_path", _i, [_p, _pd, _i64, _i, _i, ctypes.POINTER(RepairOpts), ctypes.POINTER(_pd),
                              ctypes.POINTER(_i64), ctypes.POINTER(RepairInfo)]),
     ("smp_buffer_free", None, [_p]),
+    ("smp_clearance_configs", _i, [_p, _pd, _i64, _d, _i, _i, ctypes.POINTER(Clearance),
+                                   ctypes.POINTER(ClearanceInfo)]),
+    ("smp_clearance_edges", _i, [_p, _pd, _pd, _i64, _d, _i, _i, ctypes.POINTER(EdgeClearance),
+                                 ctypes.POINTER(ClearanceInfo)]),
     ("smp_normalize_trajectory", _i, [_pd, _i64, _i, _pd, _pd, _i64, ctypes.POINTER(_i64)]),
     ("smp_ik_solve", _i, [_p, ctypes.POINTER(IkRequest), _i, ctypes.POINTER(IkResult)]),
     ("smp_find_goal_pose", _i, [_p, _pd, _pd, _d, _i, _i, _pd, ctypes.POINTER(_i), ctypes.POINTER(GoalSearch)]),

@@ -451,4 +451,119 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
 
 void smp_buffer_free(void* buffer) { std::free(buffer); }
 
+// ------------------------------------------------------------------------------------------ clearance queries
+static_assert(sizeof(smp_clearance) == sizeof(ClearDev) && sizeof(smp_edge_clearance) == sizeof(EdgeClearDev),
+              "smp_clearance and smp_edge_clearance are the kernel's records");
+
+// The widened prefilter thresholds of one call (smp_clearance.h).  SMP_ERR_ARG for a max_dist that is not finite and
+// positive, or whose largest threshold reaches the box-gap field's clamp.
+static int clear_cfg(const smp_planner* p, double D, int with_self, int with_map, ClearCfg* c) {
+  if (!std::isfinite(D) || !(D > 0.0)) return SMP_ERR_ARG;
+  std::memset(c, 0, sizeof(*c));
+  c->D = D;
+  c->with_self = with_self ? 1 : 0;
+  c->with_map = with_map ? 1 : 0;
+  if (!with_map) return SMP_OK;
+  const RobotDev& d = p->robot.dev;
+  auto threshold = [&](double r, uint32_t* out) {
+    const double a = (r + D + 1e-6) / p->scene_res;
+    const double t = std::floor(a * a);
+    if (!(t < 65535.0)) return false;
+    *out = (uint32_t)t;
+    return true;
+  };
+  for (int s = 0; s < d.n_sph; ++s)
+    if (!threshold(d.sph_r[s], &c->T[s])) return SMP_ERR_ARG;
+  for (int k = 0; k < d.n_prim; ++k) {
+    const double hz = d.prim_type[k] == 1 ? d.prim_h[k * 3 + 2] : d.prim_h[k * 3 + 1];
+    if (!threshold(std::sqrt(d.prim_rxy[k] * d.prim_rxy[k] + hz * hz), &c->pT[k])) return SMP_ERR_ARG;
+  }
+  return SMP_OK;
+}
+
+int smp_clearance_configs(smp_planner* p, const double* q_rows, int64_t n, double max_dist, int with_self, int with_map,
+                          smp_clearance* out, smp_clearance_info* info) {
+  if (!p || n < 0 || (n > 0 && (!q_rows || !out))) return SMP_ERR_ARG;
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (info) std::memset(info, 0, sizeof(*info));
+  if (int b_ = busy_check(p)) return b_;
+  if (with_map && !p->have_scene) return SMP_ERR_ARG;
+  ClearCfg cfg;
+  if (int st = clear_cfg(p, max_dist, with_self, with_map, &cfg)) return st;
+  if (n == 0) return SMP_OK;
+  if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  if (!finite_rows(q_rows, n)) return SMP_ERR_ARG;
+  const int n_items = (int)((n + CLEAR_CT - 1) / CLEAR_CT);
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(p->d_clq.reserve((size_t)n * NJ));
+  HIPCHK(p->d_clc.reserve((size_t)n));
+  HIPCHK(p->d_ecounter.reserve(1));
+  HIPCHK(hipMemcpyAsync(p->d_clq.p, q_rows, (size_t)n * NJ * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
+  const int grid = std::min(n_items, p->num_cus);  // the tile's LDS admits one workgroup per CU
+  HIPCHK(hipEventRecord(p->ev0, p->stream));
+  launch_clearance(grid, p->stream, p->d_rb, p->sc, p->d_mc, cfg, p->d_clq.p, (long long)n, nullptr, nullptr, n_items,
+                   p->d_ecounter.p, p->d_clc.p, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(p->ev1, p->stream));
+  HIPCHK(hipMemcpyAsync(out, p->d_clc.p, (size_t)n * sizeof(ClearDev), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+  p->last_check_ms = ms;
+  if (info) {
+    info->n_points = n;
+    info->kernel_ms = ms;
+    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return SMP_OK;
+}
+
+int smp_clearance_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, double max_dist,
+                        int with_self, int with_map, smp_edge_clearance* out, smp_clearance_info* info) {
+  if (!p || n < 0 || (n > 0 && (!from_rows || !to_rows || !out))) return SMP_ERR_ARG;
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (info) std::memset(info, 0, sizeof(*info));
+  if (int b_ = busy_check(p)) return b_;
+  if (with_map && !p->have_scene) return SMP_ERR_ARG;
+  ClearCfg cfg;
+  if (int st = clear_cfg(p, max_dist, with_self, with_map, &cfg)) return st;
+  if (n == 0) return SMP_OK;
+  if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  std::vector<EdgeDev> edges((size_t)n);
+  int64_t points = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!make_edge(p, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
+    points += edges[(size_t)i].M + 1;
+  }
+  std::vector<int> order((size_t)n);
+  for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return edges[x].M > edges[y].M; });
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(p->d_edges.reserve((size_t)n));
+  HIPCHK(p->d_eorder.reserve((size_t)n));
+  HIPCHK(p->d_cle.reserve((size_t)n));
+  HIPCHK(p->d_ecounter.reserve(1));
+  HIPCHK(hipMemcpyAsync(p->d_edges.p, edges.data(), (size_t)n * sizeof(EdgeDev), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemcpyAsync(p->d_eorder.p, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
+  const int grid = (int)std::min<int64_t>(n, p->num_cus);  // the tile's LDS admits one workgroup per CU
+  HIPCHK(hipEventRecord(p->ev0, p->stream));
+  launch_clearance(grid, p->stream, p->d_rb, p->sc, p->d_mc, cfg, nullptr, 0, p->d_edges.p, p->d_eorder.p, (int)n,
+                   p->d_ecounter.p, nullptr, p->d_cle.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(p->ev1, p->stream));
+  HIPCHK(hipMemcpyAsync(out, p->d_cle.p, (size_t)n * sizeof(EdgeClearDev), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+  p->last_check_ms = ms;
+  if (info) {
+    info->n_points = points;
+    info->kernel_ms = ms;
+    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return SMP_OK;
+}
+
 }  // extern "C"

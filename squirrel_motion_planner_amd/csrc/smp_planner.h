@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/smp_gpu.h"
+#include "smp_clearance.h"
 #include "smp_edges.h"
 #include "smp_host.h"
 #include "smp_ik.h"
@@ -118,6 +119,11 @@ struct smp_planner {
   // is d_ecounter
   smp::DBuf<smp::GapDev> d_gaps;
   smp::DBuf<smp::DetourDev> d_detours;
+  // clearance queries (smp_clearance_configs / smp_clearance_edges): configuration rows and per-item results; the edge
+  // table, its order and the work counter are d_edges, d_eorder and d_ecounter
+  smp::DBuf<double> d_clq;
+  smp::DBuf<smp::ClearDev> d_clc;
+  smp::DBuf<smp::EdgeClearDev> d_cle;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_check_ms = 0, last_plan_ms = 0;
   int64_t last_plan_launches = 0;

@@ -356,6 +356,56 @@ class GpuPlanner:
             lib().smp_buffer_free(out)
         return res, d
 
+    def clearance(self, q, max_dist=0.3, with_self=True, with_map=True):
+        """smp_clearance_configs: distance of every configuration to the map (capped at max_dist) and to self-collision,
+        one launch.  Returns a structured array (CLEARANCE_DTYPE: map, self, map_link, self_a, self_b; link indices
+        into robot.link_names, -1 for none); `clearance_info` keeps the call's point count and timing."""
+        q = np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1, 8))
+        out = np.zeros(len(q), CLEARANCE_DTYPE)
+        info = L.ClearanceInfo()
+        check(lib().smp_clearance_configs(self.h, q.ctypes.data_as(_pd), len(q), float(max_dist), int(with_self),
+                                          int(with_map), out.ctypes.data_as(ctypes.POINTER(L.Clearance)),
+                                          ctypes.byref(info)), "smp_clearance_configs")
+        self.clearance_info = {f: getattr(info, f) for f, _ in L.ClearanceInfo._fields_}
+        return out
+
+    def edge_clearance(self, frm, to, max_dist=0.3, with_self=True, with_map=True):
+        """smp_clearance_edges: the minima of both clearances over every dense edge frm[i] -> to[i] (the density rule of
+        smp_check_edges), the lowest points attaining them and those points' witness links, one launch.  Returns a
+        structured array (EDGE_CLEARANCE_DTYPE); `clearance_info` keeps the call's point count and timing."""
+        a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
+        b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
+        if len(a) != len(b):
+            raise ValueError("edge_clearance: %d start and %d end configurations" % (len(a), len(b)))
+        out = np.zeros(len(a), EDGE_CLEARANCE_DTYPE)
+        info = L.ClearanceInfo()
+        check(lib().smp_clearance_edges(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), float(max_dist),
+                                        int(with_self), int(with_map),
+                                        out.ctypes.data_as(ctypes.POINTER(L.EdgeClearance)), ctypes.byref(info)),
+              "smp_clearance_edges")
+        self.clearance_info = {f: getattr(info, f) for f, _ in L.ClearanceInfo._fields_}
+        return out
+
+    def path_clearance(self, waypoints, max_dist=0.3, with_self=True, with_map=True):
+        """The adjacent edges of a path through edge_clearance, and a summary: per kind the path's minimum, the first
+        edge attaining it, that edge's point and the witness link names (None where there is none).  Returns
+        (edges, summary)."""
+        w = np.asarray(waypoints, np.float64).reshape(-1, 8)
+        if len(w) < 2:
+            raise ValueError("path_clearance: a path has at least two waypoints")
+        e = self.edge_clearance(w[:-1], w[1:], max_dist, with_self, with_map)
+        names = self.robot.link_names
+        name = lambda l: names[l] if l >= 0 else None
+        im, is_ = int(np.argmin(e["map"])), int(np.argmin(e["self"]))
+        has_m, has_s = e["map_point"][im] >= 0, e["self_point"][is_] >= 0
+        summary = dict(map=float(e["map"][im]), map_edge=im if has_m else -1, map_point=int(e["map_point"][im]),
+                       map_link=name(int(e["map_link"][im])),
+                       self=float(e["self"][is_]), self_edge=is_ if has_s else -1,
+                       self_point=int(e["self_point"][is_]),
+                       self_links=(name(int(e["self_a"][is_])), name(int(e["self_b"][is_]))),
+                       n_points=int(e["n_points"].sum()))
+        return e, summary
+
     def get_collisions(self, q):
         """getCollisions (birrt_star.cpp:6910-6914): (self pairs [(link a, link b)] in pair order, map-colliding links
         in name order) of one configuration, as link names; disabled links are listed too, as in the reference."""
@@ -544,6 +594,13 @@ class GpuPlanner:
             self.h = None
 
 
+# records of GpuPlanner.clearance / edge_clearance (smp_clearance, smp_edge_clearance)
+CLEARANCE_DTYPE = np.dtype([("map", np.float64), ("self", np.float64), ("map_link", np.int32), ("self_a", np.int32),
+                            ("self_b", np.int32), ("pad", np.int32)])
+EDGE_CLEARANCE_DTYPE = np.dtype([("map", np.float64), ("self", np.float64), ("map_point", np.int32),
+                                 ("self_point", np.int32), ("map_link", np.int32), ("self_a", np.int32),
+                                 ("self_b", np.int32), ("n_points", np.int32)])
+
 # findGoalPose's endEffectorDeviations (squirrel_8dof_planner.cpp:1131-1137)
 IK_DEVIATION = [(-0.005, 0.005)] * 3 + [(-0.025, 0.025)] * 3
 
@@ -668,6 +725,33 @@ class BiRRTstarPlanner:
             return False
         trajectory[:] = [list(map(float, w)) for w in path]
         return True
+
+    def getClearance(self, joint_positions, max_dist=0.3, check_self_collision=True, check_map_collision=True):
+        """Not in the reference: the configuration's distance to the map and to self-collision with the nearest links
+        (GpuPlanner.clearance), as a dict of map, map_link, self, self_links (link names, None where there is none)."""
+        r = self._gpu.clearance([joint_positions], max_dist, check_self_collision, check_map_collision)[0]
+        names = self._gpu.robot.link_names
+        name = lambda l: names[l] if l >= 0 else None
+        return dict(map=float(r["map"]), map_link=name(int(r["map_link"])), self=float(r["self"]),
+                    self_links=(name(int(r["self_a"])), name(int(r["self_b"]))))
+
+    def getEdgeClearance(self, start_conf, end_conf, max_dist=0.3, check_self_collision=True,
+                         check_map_collision=True):
+        """The same along the dense edge start_conf -> end_conf (isEdgeValid's points): the minima, the lowest points
+        attaining them and those points' links (GpuPlanner.edge_clearance), as a dict."""
+        r = self._gpu.edge_clearance([start_conf], [end_conf], max_dist, check_self_collision, check_map_collision)[0]
+        names = self._gpu.robot.link_names
+        name = lambda l: names[l] if l >= 0 else None
+        return dict(map=float(r["map"]), map_point=int(r["map_point"]), map_link=name(int(r["map_link"])),
+                    self=float(r["self"]), self_point=int(r["self_point"]),
+                    self_links=(name(int(r["self_a"])), name(int(r["self_b"]))), n_points=int(r["n_points"]))
+
+    def getTrajectoryClearance(self, max_dist=0.3, check_self_collision=True, check_map_collision=True):
+        """GpuPlanner.path_clearance's summary for the last planned trajectory (getJointTrajectoryRef); None when it
+        has fewer than two poses."""
+        if len(self._traj) < 2:
+            return None
+        return self._gpu.path_clearance(self._traj, max_dist, check_self_collision, check_map_collision)[1]
 
     def getCollisions(self, joint_positions, self_collisions, map_collisions):
         """birrt_star.cpp:6910-6914: appends to the two lists, as the reference does."""
