@@ -280,6 +280,7 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
     need = std::max(need, check_kernels_private_bytes());
     need = std::max(need, ik_kernels_private_bytes());
     need = std::max(need, scene_kernels_private_bytes());
+    need = std::max(need, edges_kernels_private_bytes());
     need = std::max(need, repair_kernels_private_bytes());
     need = std::max(need, clearance_kernels_private_bytes());
     size_t cur = 0;

@@ -1,5 +1,7 @@
 // C ABI implementation (include/smp_gpu.h), path tools: batched dense edge checks, shortcutting, one-via detours and
-// path repair (kernels: smp_edges.hip, smp_repair.hip).
+// path repair, clearance queries (kernels: smp_edges.hip, smp_repair.hip, smp_clearance.hip).  Every entry point
+// validates, builds its tables, launches (run_pass), post-processes and fills its info record; the plain logic between
+// the launches is smp_paths.cpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,69 +11,78 @@
 #include <cstring>
 #include <vector>
 
+#include "smp_paths.h"
 #include "smp_planner.h"
 
 using namespace smp;
 
-extern "C" {
-
-// ------------------------------------------------------------------------------------------ dense edge checks
-// The density rule (include/smp_gpu.h, smp_check_edges): m hops of at most one planner step, the revolute and the
-// prismatic length each summed for joints ascending as stepTowardsRandSample does (birrt_star.cpp:5712-5868).  False
-// for a non-finite coordinate or more than SMP_EDGE_MAX_POINTS - 1 segments.
-static bool edge_density(const smp_planner* p, const double* a, const double* b, int* m_out) {
-  const int* rev = p->robot.dev.rev;
-  double sr = 0.0, sp = 0.0;
-  for (int j = 0; j < NJ; ++j) {
-    if (!std::isfinite(a[j]) || !std::isfinite(b[j])) return false;
-    const double d = b[j] - a[j];
-    if (rev[j]) sr += d * d; else sp += d * d;
-  }
-  const double lr = std::sqrt(sr), lp = std::sqrt(sp);
-  const double x = std::ceil(std::max(lr, lp) / p->params.step_factor);
-  if (!(x * p->params.num_traj_segments <= (double)(SMP_EDGE_MAX_POINTS - 1))) return false;
-  *m_out = x < 1.0 ? 1 : (int)x;
-  return true;
-}
-
-static bool make_edge(const smp_planner* p, const double* a, const double* b, EdgeDev* e) {
-  int m = 0;
-  if (!edge_density(p, a, b, &m)) return false;
-  for (int j = 0; j < NJ; ++j) { e->a[j] = a[j]; e->b[j] = b[j]; }
-  e->M = p->params.num_traj_segments * m;
-  e->pad = 0;
-  return true;
-}
-
-// One edges_kernel launch over the table: first[i] = first colliding point of edge i, -1 if it is free.  The
-// workgroups draw the edges longest first from a counter zeroed on the stream.
-static int run_edges(smp_planner* p, const std::vector<EdgeDev>& edges, int self, int map, std::vector<int>& first,
-                     double* kernel_ms) {
-  const size_t n = edges.size();
-  std::vector<int> order(n);
-  for (size_t i = 0; i < n; ++i) order[i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return edges[x].M > edges[y].M; });
-  first.assign(n, -1);
+// ------------------------------------------------------------------------------------------ one launch of a pass
+// The launch protocol of every pass kernel (smp_pass.h's ticket_loop): the uploads, the work counter zeroed on the
+// stream, the launch between the two events on min(n_items, CUs) workgroups -- the tiles' LDS admits one per CU --,
+// the download, and the kernel's time once the stream is idle.  upload() reserves and fills the call's device tables
+// and returns a status, launch(grid) starts the kernel, and the n_out records it leaves in d_out are copied to out.
+template <typename T, typename Upload, typename Launch>
+static int run_pass(smp_planner* p, size_t n_items, Upload&& upload, Launch&& launch, DBuf<T>& d_out, void* out,
+                    size_t n_out, double* kernel_ms) {
   HIPCHK(hipSetDevice(p->device));
-  HIPCHK(p->d_edges.reserve(n));
-  HIPCHK(p->d_eorder.reserve(n));
-  HIPCHK(p->d_efirst.reserve(n));
   HIPCHK(p->d_ecounter.reserve(1));
-  HIPCHK(hipMemcpyAsync(p->d_edges.p, edges.data(), n * sizeof(EdgeDev), hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemcpyAsync(p->d_eorder.p, order.data(), n * sizeof(int), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(d_out.reserve(n_out));
+  if (int st = upload()) return st;
   HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
-  const int grid = (int)std::min<size_t>(n, (size_t)p->num_cus);  // the tile's LDS admits one workgroup per CU
+  const int grid = (int)std::min<size_t>(n_items, (size_t)p->num_cus);
   HIPCHK(hipEventRecord(p->ev0, p->stream));
-  launch_edges(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_edges.p, p->d_eorder.p, (int)n, self,
-               map && p->have_scene, p->d_ecounter.p, p->d_efirst.p);
+  launch(grid);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(p->ev1, p->stream));
-  HIPCHK(hipMemcpyAsync(first.data(), p->d_efirst.p, n * sizeof(int), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipMemcpyAsync(out, d_out.p, n_out * sizeof(T), hipMemcpyDeviceToHost, p->stream));
   HIPCHK(hipStreamSynchronize(p->stream));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-  if (kernel_ms) *kernel_ms = ms;
+  *kernel_ms = ms;
   return SMP_OK;
+}
+
+// The two times every info record ends with.
+template <typename Info>
+static void fill_times(Info* info, double kernel_ms, std::chrono::steady_clock::time_point t_begin) {
+  info->kernel_ms = kernel_ms;
+  info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+}
+
+static EdgeRule edge_rule(const smp_planner* p) {
+  return EdgeRule{p->robot.dev.rev, p->params.step_factor, p->params.num_traj_segments, SMP_EDGE_MAX_POINTS};
+}
+
+// n records into a device table that grows to hold them (an upload of run_pass).
+template <typename T>
+static int upload(smp_planner* p, DBuf<T>& d, const T* src, size_t n) {
+  HIPCHK(d.reserve(n));
+  HIPCHK(hipMemcpyAsync(d.p, src, n * sizeof(T), hipMemcpyHostToDevice, p->stream));
+  return SMP_OK;
+}
+
+// The edge table and its longest-first order into d_edges and d_eorder.
+static int upload_edges(smp_planner* p, const std::vector<EdgeDev>& edges, const std::vector<int>& order) {
+  if (int st = upload(p, p->d_edges, edges.data(), edges.size())) return st;
+  return upload(p, p->d_eorder, order.data(), order.size());
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------ dense edge checks
+// One edges_kernel launch over the table: first[i] = first colliding point of edge i, -1 if it is free.
+static int run_edges(smp_planner* p, const std::vector<EdgeDev>& edges, int self, int map, std::vector<int>& first,
+                     double* kernel_ms) {
+  const size_t n = edges.size();
+  const std::vector<int> order = longest_first(edges);
+  first.assign(n, -1);
+  return run_pass(
+      p, n, [&] { return upload_edges(p, edges, order); },
+      [&](int grid) {
+        launch_edges(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_edges.p, p->d_eorder.p, (int)n, self,
+                     map && p->have_scene, p->d_ecounter.p, p->d_efirst.p);
+      },
+      p->d_efirst, first.data(), n, kernel_ms);
 }
 
 // Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule.
@@ -82,9 +93,10 @@ int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_ro
   if (n == 0) return SMP_OK;
   if (check_map && !p->have_scene) return SMP_ERR_ARG;
   if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  const EdgeRule rule = edge_rule(p);
   std::vector<EdgeDev> edges((size_t)n);
   for (int64_t i = 0; i < n; ++i)
-    if (!make_edge(p, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
+    if (!make_edge(rule, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
   std::vector<int> first;
   double ms = 0;
   const int st = run_edges(p, edges, check_self, check_map, first, &ms);
@@ -112,83 +124,26 @@ int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int ch
   if (int b_ = busy_check(p)) return b_;
   if (check_map && !p->have_scene) return SMP_ERR_ARG;
   if (k > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
-  const int64_t w = (window <= 0 || window > k - 1) ? k - 1 : window;
-  // candidates (i, j), i < j <= i + w, in the order of the dynamic program: j ascending, then i ascending
-  const int64_t n_edges = w * (k - 1) - w * (w - 1) / 2;
+  const int64_t w = shortcut_window(k, window);
+  const int64_t n_edges = shortcut_candidates(k, w);
   if (n_edges > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
-  std::vector<EdgeDev> edges((size_t)n_edges);
-  {
-    size_t e = 0;
-    for (int64_t j = 1; j < k; ++j)
-      for (int64_t i = std::max<int64_t>(0, j - w); i < j; ++i, ++e)
-        if (!make_edge(p, waypoints + i * NJ, waypoints + j * NJ, &edges[e])) return SMP_ERR_ARG;
-  }
+  std::vector<EdgeDev> edges;
+  if (!shortcut_edges(edge_rule(p), waypoints, k, w, &edges)) return SMP_ERR_ARG;
   std::vector<int> first;
   double ms = 0;
   const int st = run_edges(p, edges, check_self, check_map, first, &ms);
   if (st != SMP_OK) return st;
-  auto dist = [&](int64_t i, int64_t j) {  // DH:128-156
-    double s = 0.0;
-    for (int c = 0; c < NJ; ++c) {
-      const double d = waypoints[j * NJ + c] - waypoints[i * NJ + c];
-      s += d * d;
-    }
-    return std::sqrt(s);
-  };
-  std::vector<double> dp((size_t)k, HUGE_VAL);
-  std::vector<int64_t> pred((size_t)k, -1), pred_edge((size_t)k, -1);
-  dp[0] = 0.0;
-  int64_t n_valid = 0, checked = 0, first_blocked = -1;
-  double cost_in = 0.0;
-  {
-    size_t e = 0;
-    for (int64_t j = 1; j < k; ++j) {
-      cost_in += dist(j - 1, j);
-      for (int64_t i = std::max<int64_t>(0, j - w); i < j; ++i, ++e) {
-        const int f = first[e];
-        checked += f < 0 ? edges[e].M + 1 : f + 1;
-        if (f >= 0) {
-          if (i == j - 1 && first_blocked < 0) first_blocked = i;
-          continue;
-        }
-        ++n_valid;
-        const double c = dp[(size_t)i] + dist(i, j);
-        if (c < dp[(size_t)j]) { dp[(size_t)j] = c; pred[(size_t)j] = i; pred_edge[(size_t)j] = (int64_t)e; }
-      }
-    }
-  }
-  const bool reached = pred[(size_t)(k - 1)] >= 0;
+  smp_shortcut_info s;
+  const std::vector<EdgeDev> route = shortcut_route(waypoints, k, w, edges, first, &s);
   int rc = SMP_ERR_NO_SOLUTION;
-  if (reached) {
-    std::vector<int64_t> route;  // edge indices, goal to start
-    for (int64_t j = k - 1; j > 0; j = pred[(size_t)j]) route.push_back(pred_edge[(size_t)j]);
-    const int nseg = p->params.num_traj_segments;
-    int64_t rows = 1;
-    for (int64_t e : route) rows += edges[(size_t)e].M / nseg;
-    double* out = static_cast<double*>(std::malloc((size_t)rows * NJ * sizeof(double)));
-    if (!out) return SMP_ERR_CAPACITY;
-    int64_t r = 0;
-    for (size_t t = route.size(); t-- > 0;) {
-      const EdgeDev& ed = edges[(size_t)route[t]];
-      double step[NJ];
-      for (int c = 0; c < NJ; ++c) step[c] = (ed.b[c] - ed.a[c]) / (double)ed.M;
-      for (int h = 0; h < ed.M; h += nseg, ++r)  // the start waypoint (h = 0), then the via nodes
-        for (int c = 0; c < NJ; ++c) out[r * NJ + c] = h == 0 ? ed.a[c] : ed.a[c] + (double)h * step[c];
-    }
-    for (int c = 0; c < NJ; ++c) out[r * NJ + c] = waypoints[(k - 1) * NJ + c];
-    *out_waypoints = out;
-    *n_out = rows;
+  if (!route.empty()) {
+    *out_waypoints = route_rows(route, p->params.num_traj_segments, n_out);
+    if (!*out_waypoints) return SMP_ERR_CAPACITY;
     rc = SMP_OK;
   }
   if (info) {
-    info->n_edges = n_edges;
-    info->n_valid = n_valid;
-    info->configs_checked = checked;
-    info->cost_in = cost_in;
-    info->cost_out = reached ? dp[(size_t)(k - 1)] : 0.0;
-    info->first_blocked = reached ? -1 : first_blocked;
-    info->kernel_ms = ms;
-    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    *info = s;
+    fill_times(info, ms, t_begin);
   }
   p->last_check_ms = ms;
   return rc;
@@ -197,39 +152,26 @@ int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int ch
 // ------------------------------------------------------------------------------------------ path repair
 static_assert(sizeof(smp_detour) == sizeof(DetourDev), "smp_detour is the kernel's record");
 
-// One detours_kernel launch: out[g * samples + s] for the gaps of the table, items drawn from a counter zeroed on the
-// stream.
+// One detours_kernel launch: out[g * samples + s] for the gaps of the table.
 static int run_detours(smp_planner* p, const std::vector<GapDev>& gaps, int samples, double h, uint64_t seed,
                        uint32_t round, int self, int map, DetourDev* out, double* kernel_ms) {
   const size_t n_items = gaps.size() * (size_t)samples;
-  HIPCHK(hipSetDevice(p->device));
-  HIPCHK(p->d_gaps.reserve(gaps.size()));
-  HIPCHK(p->d_detours.reserve(n_items));
-  HIPCHK(p->d_ecounter.reserve(1));
-  HIPCHK(hipMemcpyAsync(p->d_gaps.p, gaps.data(), gaps.size() * sizeof(GapDev), hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
-  DetourArgs a;
-  a.n_items = (int)n_items;
-  a.samples = samples;
-  a.n_seg = p->params.num_traj_segments;
-  a.max_points = SMP_EDGE_MAX_POINTS;
-  a.self = self;
-  a.map = map && p->have_scene;
-  a.round = round;
-  a.seed = seed;
-  a.step = p->params.step_factor;
-  a.h = h;
-  const int grid = (int)std::min<size_t>(n_items, (size_t)p->num_cus);  // the tile's LDS admits one workgroup per CU
-  HIPCHK(hipEventRecord(p->ev0, p->stream));
-  launch_detours(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_gaps.p, a, p->d_ecounter.p, p->d_detours.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(p->ev1, p->stream));
-  HIPCHK(hipMemcpyAsync(out, p->d_detours.p, n_items * sizeof(DetourDev), hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipStreamSynchronize(p->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-  if (kernel_ms) *kernel_ms = ms;
-  return SMP_OK;
+  const DetourArgs a{(int)n_items, samples, p->params.num_traj_segments, SMP_EDGE_MAX_POINTS, self,
+                     map && p->have_scene, round, seed, p->params.step_factor, h};
+  return run_pass(
+      p, n_items, [&] { return upload(p, p->d_gaps, gaps.data(), gaps.size()); },
+      [&](int grid) {
+        launch_detours(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_gaps.p, a, p->d_ecounter.p, p->d_detours.p);
+      },
+      p->d_detours, out, n_items, kernel_ms);
+}
+
+static GapDev make_gap(const double* a, const double* b, unsigned g) {
+  GapDev d;
+  for (int j = 0; j < NJ; ++j) { d.a[j] = a[j]; d.b[j] = b[j]; }
+  d.g = g;
+  d.pad = 0;
+  return d;
 }
 
 static bool finite_rows(const double* rows, int64_t n) {
@@ -249,14 +191,7 @@ int smp_sample_detours(smp_planner* p, const double* from_rows, const double* to
   if (n_gaps > SMP_EDGE_TABLE_MAX || n_gaps * (int64_t)samples > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   if (!finite_rows(from_rows, n_gaps) || !finite_rows(to_rows, n_gaps)) return SMP_ERR_ARG;
   std::vector<GapDev> gaps((size_t)n_gaps);
-  for (int64_t g = 0; g < n_gaps; ++g) {
-    for (int j = 0; j < NJ; ++j) {
-      gaps[(size_t)g].a[j] = from_rows[g * NJ + j];
-      gaps[(size_t)g].b[j] = to_rows[g * NJ + j];
-    }
-    gaps[(size_t)g].g = (unsigned)g;
-    gaps[(size_t)g].pad = 0;
-  }
+  for (int64_t g = 0; g < n_gaps; ++g) gaps[(size_t)g] = make_gap(from_rows + g * NJ, to_rows + g * NJ, (unsigned)g);
   double ms = 0;
   const int st = run_detours(p, gaps, samples, half_width, seed, round, check_self, check_map,
                              reinterpret_cast<DetourDev*>(out), &ms);
@@ -293,14 +228,7 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
   if (k > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   if (!finite_rows(waypoints, k)) return SMP_ERR_ARG;
   auto W = [&](int64_t i) { return waypoints + i * NJ; };
-  auto dist = [](const double* a, const double* b) {  // DH:128-156
-    double s = 0.0;
-    for (int c = 0; c < NJ; ++c) {
-      const double d = b[c] - a[c];
-      s += d * d;
-    }
-    return std::sqrt(s);
-  };
+  const EdgeRule rule = edge_rule(p);
   double kernel_ms = 0, ms = 0;
   // 1. validity of the waypoints and of the adjacent edges
   std::vector<uint8_t> valid((size_t)k);
@@ -316,134 +244,55 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
   if (!valid[(size_t)(k - 1)]) return SMP_ERR_GOAL_INVALID;
   std::vector<EdgeDev> edges((size_t)(k - 1));
   for (int64_t i = 0; i + 1 < k; ++i)
-    if (!make_edge(p, W(i), W(i + 1), &edges[(size_t)i])) return SMP_ERR_ARG;
+    if (!make_edge(rule, W(i), W(i + 1), &edges[(size_t)i])) return SMP_ERR_ARG;
   std::vector<int> first;
   {
     const int st = run_edges(p, edges, check_self, check_map, first, &ms);
     if (st != SMP_OK) return st;
     kernel_ms += ms;
   }
-  // 2. gaps: (l, r) waypoint indices of the anchors, e = the gap's smallest blocked edge
-  struct Gap { int64_t l, r, e; bool open; double v[NJ]; };
-  std::vector<Gap> gaps;
-  int64_t n_blocked = 0;
-  double cost_in = 0.0;
-  for (int64_t i = 0; i + 1 < k; ++i) {
-    cost_in += dist(W(i), W(i + 1));
-    if (first[(size_t)i] < 0) continue;
-    ++n_blocked;
-    int64_t l = i, r = i + 1;
-    while (!valid[(size_t)l]) --l;  // w_0 and w_k-1 are valid
-    while (!valid[(size_t)r]) ++r;
-    if (!gaps.empty() && l < gaps.back().r) {
-      gaps.back().r = std::max(gaps.back().r, r);
-    } else {
-      Gap g{};
-      g.l = l; g.r = r; g.e = i; g.open = true;
-      gaps.push_back(g);
-    }
-  }
-  const int64_t n_gaps = (int64_t)gaps.size();
+  // 2. gaps (both end waypoints are valid here, as find_gaps requires); r is what *info receives
+  smp_repair_info r{};
+  r.first_blocked = -1;
+  std::vector<Gap> gaps = find_gaps(valid.data(), first.data(), k, &r.n_blocked_edges);
+  for (int64_t i = 0; i + 1 < k; ++i) r.cost_in += dist(W(i), W(i + 1));
+  const int64_t n_gaps = r.n_gaps = (int64_t)gaps.size();
   if (n_gaps * (int64_t)o.samples > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   // 3. rounds over the gaps still open
-  int64_t n_items = 0, n_free = 0, n_open = n_gaps;
-  int rounds_used = 0;
+  int64_t n_open = n_gaps;
   std::vector<GapDev> table;
   std::vector<DetourDev> items;
   for (int rho = 0; rho < o.rounds && n_open > 0; ++rho) {
     table.clear();
-    for (int64_t g = 0; g < n_gaps; ++g) {
-      if (!gaps[(size_t)g].open) continue;
-      GapDev d;
-      for (int j = 0; j < NJ; ++j) {
-        d.a[j] = W(gaps[(size_t)g].l)[j];
-        d.b[j] = W(gaps[(size_t)g].r)[j];
-      }
-      d.g = (unsigned)g;
-      d.pad = 0;
-      table.push_back(d);
-    }
+    for (int64_t g = 0; g < n_gaps; ++g)
+      if (gaps[(size_t)g].open) table.push_back(make_gap(W(gaps[(size_t)g].l), W(gaps[(size_t)g].r), (unsigned)g));
     items.resize(table.size() * (size_t)o.samples);
     const double h = std::ldexp(p->params.step_factor, rho);
     const int st = run_detours(p, table, o.samples, h, o.seed, (uint32_t)rho, check_self, check_map, items.data(), &ms);
     if (st != SMP_OK) return st;
     kernel_ms += ms;
-    ++rounds_used;
-    n_items += (int64_t)items.size();
-    for (size_t t = 0; t < table.size(); ++t) {
-      Gap& g = gaps[table[t].g];
-      double best = HUGE_VAL;
-      int chosen = -1;
-      for (int s = 0; s < o.samples; ++s) {
-        const DetourDev& it = items[t * (size_t)o.samples + (size_t)s];
-        if (!it.free) continue;
-        ++n_free;
-        const double c = dist(table[t].a, it.v) + dist(it.v, table[t].b);
-        if (c < best) { best = c; chosen = s; }
-      }
-      if (chosen >= 0) {
-        for (int j = 0; j < NJ; ++j) g.v[j] = items[t * (size_t)o.samples + (size_t)chosen].v[j];
-        g.open = false;
+    ++r.rounds_used;
+    r.n_items += (int64_t)items.size();
+    for (size_t t = 0; t < table.size(); ++t)
+      if (close_gap(&gaps[table[t].g], table[t].a, table[t].b, &items[t * (size_t)o.samples], o.samples, &r.n_free) >= 0)
         --n_open;
-      }
-    }
   }
   int rc = SMP_OK;
-  int64_t first_blocked = -1;
-  double cost_out = 0.0;
   if (n_open > 0) {
     rc = SMP_ERR_NO_SOLUTION;  // 4.
     for (const Gap& g : gaps)
-      if (g.open) { first_blocked = g.e; break; }
+      if (g.open) { r.first_blocked = g.e; break; }
   } else {
     // 5. the route's rows, then the via nodes of every route edge between them
-    std::vector<const double*> route;
-    {
-      size_t g = 0;
-      for (int64_t i = 0; i < k;) {
-        route.push_back(W(i));
-        if (g < gaps.size() && gaps[g].l == i) {
-          route.push_back(gaps[g].v);
-          i = gaps[g].r;
-          ++g;
-        } else {
-          ++i;
-        }
-      }
-    }
-    const int nseg = p->params.num_traj_segments;
-    std::vector<EdgeDev> re(route.size() - 1);
-    int64_t rows = 1;
-    for (size_t t = 0; t + 1 < route.size(); ++t) {
-      if (!make_edge(p, route[t], route[t + 1], &re[t])) return SMP_ERR_ARG;
-      rows += re[t].M / nseg;
-      cost_out += dist(route[t], route[t + 1]);
-    }
-    double* out = static_cast<double*>(std::malloc((size_t)rows * NJ * sizeof(double)));
-    if (!out) return SMP_ERR_CAPACITY;
-    int64_t r = 0;
-    for (const EdgeDev& ed : re) {
-      double step[NJ];
-      for (int c = 0; c < NJ; ++c) step[c] = (ed.b[c] - ed.a[c]) / (double)ed.M;
-      for (int h = 0; h < ed.M; h += nseg, ++r)  // the edge's start (h = 0), then its via nodes
-        for (int c = 0; c < NJ; ++c) out[r * NJ + c] = h == 0 ? ed.a[c] : ed.a[c] + (double)h * step[c];
-    }
-    for (int c = 0; c < NJ; ++c) out[r * NJ + c] = W(k - 1)[c];
-    *out_waypoints = out;
-    *n_out = rows;
+    std::vector<EdgeDev> route;
+    if (!repaired_route(rule, waypoints, k, gaps, &route, &r.cost_out)) return SMP_ERR_ARG;
+    *out_waypoints = route_rows(route, p->params.num_traj_segments, n_out);
+    if (!*out_waypoints) return SMP_ERR_CAPACITY;
   }
+  r.n_repaired = n_gaps - n_open;
   if (info) {
-    info->n_blocked_edges = n_blocked;
-    info->n_gaps = n_gaps;
-    info->n_repaired = n_gaps - n_open;
-    info->n_items = n_items;
-    info->n_free = n_free;
-    info->rounds_used = rounds_used;
-    info->cost_in = cost_in;
-    info->cost_out = cost_out;
-    info->first_blocked = first_blocked;
-    info->kernel_ms = kernel_ms;
-    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    *info = r;
+    fill_times(info, kernel_ms, t_begin);
   }
   p->last_check_ms = kernel_ms;
   return rc;
@@ -481,6 +330,17 @@ static int clear_cfg(const smp_planner* p, double D, int with_self, int with_map
   return SMP_OK;
 }
 
+// What a clearance call leaves behind once its launch succeeded.
+static int clearance_done(smp_planner* p, smp_clearance_info* info, int64_t points, double ms,
+                          std::chrono::steady_clock::time_point t_begin) {
+  p->last_check_ms = ms;
+  if (info) {
+    info->n_points = points;
+    fill_times(info, ms, t_begin);
+  }
+  return SMP_OK;
+}
+
 int smp_clearance_configs(smp_planner* p, const double* q_rows, int64_t n, double max_dist, int with_self, int with_map,
                           smp_clearance* out, smp_clearance_info* info) {
   if (!p || n < 0 || (n > 0 && (!q_rows || !out))) return SMP_ERR_ARG;
@@ -493,30 +353,16 @@ int smp_clearance_configs(smp_planner* p, const double* q_rows, int64_t n, doubl
   if (n == 0) return SMP_OK;
   if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   if (!finite_rows(q_rows, n)) return SMP_ERR_ARG;
-  const int n_items = (int)((n + CLEAR_CT - 1) / CLEAR_CT);
-  HIPCHK(hipSetDevice(p->device));
-  HIPCHK(p->d_clq.reserve((size_t)n * NJ));
-  HIPCHK(p->d_clc.reserve((size_t)n));
-  HIPCHK(p->d_ecounter.reserve(1));
-  HIPCHK(hipMemcpyAsync(p->d_clq.p, q_rows, (size_t)n * NJ * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
-  const int grid = std::min(n_items, p->num_cus);  // the tile's LDS admits one workgroup per CU
-  HIPCHK(hipEventRecord(p->ev0, p->stream));
-  launch_clearance(grid, p->stream, p->d_rb, p->sc, p->d_mc, cfg, p->d_clq.p, (long long)n, nullptr, nullptr, n_items,
-                   p->d_ecounter.p, p->d_clc.p, nullptr);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(p->ev1, p->stream));
-  HIPCHK(hipMemcpyAsync(out, p->d_clc.p, (size_t)n * sizeof(ClearDev), hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipStreamSynchronize(p->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-  p->last_check_ms = ms;
-  if (info) {
-    info->n_points = n;
-    info->kernel_ms = ms;
-    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return SMP_OK;
+  const int n_items = (int)((n + PASS_CT - 1) / PASS_CT);
+  double ms = 0;
+  const int st = run_pass(
+      p, (size_t)n_items, [&] { return upload(p, p->d_clq, q_rows, (size_t)n * NJ); },
+      [&](int grid) {
+        launch_clearance(grid, p->stream, p->d_rb, p->sc, p->d_mc, cfg, p->d_clq.p, (long long)n, nullptr, nullptr,
+                         n_items, p->d_ecounter.p, p->d_clc.p, nullptr);
+      },
+      p->d_clc, out, (size_t)n, &ms);
+  return st != SMP_OK ? st : clearance_done(p, info, n, ms, t_begin);
 }
 
 int smp_clearance_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, double max_dist,
@@ -530,40 +376,23 @@ int smp_clearance_edges(smp_planner* p, const double* from_rows, const double* t
   if (int st = clear_cfg(p, max_dist, with_self, with_map, &cfg)) return st;
   if (n == 0) return SMP_OK;
   if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  const EdgeRule rule = edge_rule(p);
   std::vector<EdgeDev> edges((size_t)n);
   int64_t points = 0;
   for (int64_t i = 0; i < n; ++i) {
-    if (!make_edge(p, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
+    if (!make_edge(rule, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
     points += edges[(size_t)i].M + 1;
   }
-  std::vector<int> order((size_t)n);
-  for (int64_t i = 0; i < n; ++i) order[(size_t)i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return edges[x].M > edges[y].M; });
-  HIPCHK(hipSetDevice(p->device));
-  HIPCHK(p->d_edges.reserve((size_t)n));
-  HIPCHK(p->d_eorder.reserve((size_t)n));
-  HIPCHK(p->d_cle.reserve((size_t)n));
-  HIPCHK(p->d_ecounter.reserve(1));
-  HIPCHK(hipMemcpyAsync(p->d_edges.p, edges.data(), (size_t)n * sizeof(EdgeDev), hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemcpyAsync(p->d_eorder.p, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemsetAsync(p->d_ecounter.p, 0, sizeof(unsigned), p->stream));
-  const int grid = (int)std::min<int64_t>(n, p->num_cus);  // the tile's LDS admits one workgroup per CU
-  HIPCHK(hipEventRecord(p->ev0, p->stream));
-  launch_clearance(grid, p->stream, p->d_rb, p->sc, p->d_mc, cfg, nullptr, 0, p->d_edges.p, p->d_eorder.p, (int)n,
-                   p->d_ecounter.p, nullptr, p->d_cle.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(p->ev1, p->stream));
-  HIPCHK(hipMemcpyAsync(out, p->d_cle.p, (size_t)n * sizeof(EdgeClearDev), hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipStreamSynchronize(p->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-  p->last_check_ms = ms;
-  if (info) {
-    info->n_points = points;
-    info->kernel_ms = ms;
-    info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return SMP_OK;
+  const std::vector<int> order = longest_first(edges);
+  double ms = 0;
+  const int st = run_pass(
+      p, (size_t)n, [&] { return upload_edges(p, edges, order); },
+      [&](int grid) {
+        launch_clearance(grid, p->stream, p->d_rb, p->sc, p->d_mc, cfg, nullptr, 0, p->d_edges.p, p->d_eorder.p, (int)n,
+                         p->d_ecounter.p, nullptr, p->d_cle.p);
+      },
+      p->d_cle, out, (size_t)n, &ms);
+  return st != SMP_OK ? st : clearance_done(p, info, points, ms, t_begin);
 }
 
 }  // extern "C"

@@ -4,12 +4,10 @@
 
 #include <hip/hip_runtime.h>
 
-#include "smp_edges.h"
+#include "smp_pass.h"
 #include "smp_types.h"
 
 namespace smp {
-
-constexpr int CLEAR_CT = 32;  // configurations per tile (the edge kernel's EDGES_CT)
 
 // Per call: the query distance and the widened prefilter thresholds it gives (formed on the host).
 // T[s]  = floor(((r_s + D + 1e-6) / res)^2): the box-gap field at the sphere's centre cell above it means the sphere's
@@ -35,7 +33,8 @@ struct EdgeClearDev {
 static_assert(sizeof(ClearDev) == 32 && sizeof(EdgeClearDev) == 40, "the C ABI's records");
 
 // One launch over n_items items drawn from *counter (zeroed on the stream before the launch).
-//   edges == nullptr: item t is the tile of configurations 32 t .. min(32 t + 31, n - 1) of q_rows (row-major n x 8),
+//   edges == nullptr: item t is the tile of configurations 32 t .. min(32 t + 31, n - 1) (PASS_CT each) of q_rows
+//                     (row-major n x 8),
 //                     out_c[i] per configuration;
 //   else:             item t is edge order[t] of the table (n = n_items edges), out_e[e] per edge.
 void launch_clearance(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const ClearCfg& cfg,

@@ -3,8 +3,8 @@
 //
 // The collision tiles stop at the first hit; here every test becomes a minimum with its witness over a reach widened by
 // the query distance D.  One workgroup takes one item at a time from an atomic work counter -- a tile of 32 consecutive
-// configurations, or one edge of the density rule walked in tiles of 32 points with running minima -- in edges_kernel's
-// work loop.  Per tile:
+// configurations, or one edge of the density rule walked in tiles of 32 points with running minima -- in the passes'
+// work loop (ticket_loop, smp_pass.h).  Per tile:
 //   1. body frames, one lane per configuration, in the checker's arithmetic (body_frames' loop, storing into LDS);
 //   2. lanes over (configuration, sphere) and (configuration, primitive): world centres, and the box-gap field d2 at the
 //      centre cell against the widened threshold -- the loads of all items issued together; what passes is listed;
@@ -21,27 +21,28 @@
 #include "smp_clearance.h"
 #include "smp_collide.h"
 #include "smp_math.h"
+#include "smp_pass.h"
 #include "smp_types.h"
 
 namespace smp {
 
 constexpr int CL_ITEMS = MAX_SPH + MAX_PRIM;  // map items of one configuration: sphere s, then MAX_SPH + primitive p
-constexpr int CL_CPW = CLEAR_CT / NWAVE;      // configurations per wavefront in the self test and the reductions
-constexpr int CL_MAXU = (CLEAR_CT * MAX_SPH + BLOCK - 1) / BLOCK;  // (configuration, sphere) items per lane
+constexpr int CL_CPW = PASS_CT / NWAVE;      // configurations per wavefront in the self test and the reductions
+constexpr int CL_MAXU = (PASS_CT * MAX_SPH + BLOCK - 1) / BLOCK;  // (configuration, sphere) items per lane
 
 struct ClearLds {
-  double fr[CLEAR_CT][MAX_BODY][12];   // body frames (R row-major, p)
-  double wc[CLEAR_CT][MAX_SPH][3];     // sphere world centres
-  double pw[CLEAR_CT][MAX_PRIM][5];    // primitive centres and x axes
-  double mterm[CLEAR_CT][CL_ITEMS];    // map term of every item, min(D, .)
-  double c_map[CLEAR_CT], c_self[CLEAR_CT];  // per configuration: the two minima ...
-  int c_link[CLEAR_CT], c_key[CLEAR_CT];     // ... the map witness link, the self witness a << 10 | b
-  uint16_t cand[CLEAR_CT * CL_ITEMS];  // items that passed the prefilter: configuration << 8 | item
-  uint16_t cand_d2[CLEAR_CT * CL_ITEMS];  // ... and d2 at their centre cell (65535: none, the centre is off the grid in z)
+  double fr[PASS_CT][MAX_BODY][12];   // body frames (R row-major, p)
+  double wc[PASS_CT][MAX_SPH][3];     // sphere world centres
+  double pw[PASS_CT][MAX_PRIM][5];    // primitive centres and x axes
+  double mterm[PASS_CT][CL_ITEMS];    // map term of every item, min(D, .)
+  double c_map[PASS_CT], c_self[PASS_CT];  // per configuration: the two minima ...
+  int c_link[PASS_CT], c_key[PASS_CT];     // ... the map witness link, the self witness a << 10 | b
+  uint16_t cand[PASS_CT * CL_ITEMS];  // items that passed the prefilter: configuration << 8 | item
+  uint16_t cand_d2[PASS_CT * CL_ITEMS];  // ... and d2 at their centre cell (65535: none, the centre is off the grid in z)
   unsigned ncand;
 };
-static_assert(CLEAR_CT <= 64 && CL_ITEMS <= 128 && CL_ITEMS <= 256, "item codes; two items per lane in the reduction");
-static_assert(CLEAR_CT % NWAVE == 0, "tile size");
+static_assert(PASS_CT <= 64 && CL_ITEMS <= 128 && CL_ITEMS <= 256, "item codes; two items per lane in the reduction");
+static_assert(PASS_CT % NWAVE == 0, "tile size");
 
 // Lexicographic minimum of (v, k) over the 64 lanes of a wavefront (all active); every lane receives it.
 __device__ __forceinline__ void wave_min_key(double& v, int& k) {
@@ -351,7 +352,7 @@ __device__ __forceinline__ double prim_term(const SceneDev& sc, int ty, const do
   return t < D ? t : D;
 }
 
-// Clearance of nc <= CLEAR_CT configurations q_lds[c], all block threads.  On return (after a block barrier)
+// Clearance of nc <= PASS_CT configurations q_lds[c], all block threads.  On return (after a block barrier)
 // L.c_map / c_link / c_self / c_key hold the results of configurations 0 .. nc - 1.
 __device__ __forceinline__ void clearance_tile(const RobotDev* __restrict__ rb, const SceneDev& sc,
                                                const MapCfg* __restrict__ mc, const ClearCfg& cfg, int nc,
@@ -542,94 +543,89 @@ __global__ void __launch_bounds__(BLOCK) clearance_kernel(const RobotDev* __rest
   __shared__ RobotDev s_rb;
   __shared__ MapCfg s_mc;
   __shared__ ClearLds L;
-  __shared__ double ql[CLEAR_CT][NJ];
+  __shared__ double ql[PASS_CT][NJ];
   __shared__ double ea[NJ], es[NJ];  // the edge's start and its step (b - a) / M
-  __shared__ unsigned s_slot;
   const int tid = threadIdx.x;
   stage_model(rb, mc, &s_rb, &s_mc);  // (ends with a barrier)
   const SceneDev sc = uniform_scene(sc_in);
-  // edges_kernel's work loop: thread 0's work of one round -- the result of the item just done and the next ticket -- is
-  // one block followed by a barrier, and the slot reaches the loop condition through readfirstlane
-  if (tid == 0) s_slot = atomicAdd(counter, 1u);
-  __syncthreads();
-  unsigned slot = (unsigned)__builtin_amdgcn_readfirstlane((int)s_slot);
-  while (slot < (unsigned)n_items) {
-    int e = 0, M;
-    long long q0 = 0;
-    if (edges) {
-      e = __builtin_amdgcn_readfirstlane(order[slot]);
-      M = __builtin_amdgcn_readfirstlane(edges[e].M);
-      if (tid < NJ) {
-        const double a = edges[e].a[tid], b = edges[e].b[tid];
-        ea[tid] = a;
-        es[tid] = (b - a) / (double)M;
-      }
-    } else {
-      q0 = (long long)slot * CLEAR_CT;
-      M = __builtin_amdgcn_readfirstlane((int)min((long long)CLEAR_CT, n - q0)) - 1;
-    }
-    __syncthreads();
-    // running minima of an edge (wave 0, the same in all its lanes)
-    double r_map = cfg.D, r_self = HUGE_VAL;
-    int r_mpt = -1, r_mlink = -1, r_spt = -1, r_skey = -1;
-    for (int base = 0; base <= M; base += CLEAR_CT) {
-      const int nc = __builtin_amdgcn_readfirstlane(min(CLEAR_CT, M + 1 - base));
-      for (int it = tid; it < nc * NJ; it += BLOCK) {
-        const int c = it / NJ, j = it - c * NJ;
-        ql[c][j] = edges ? ea[j] + (double)(base + c) * es[j] : q_rows[(q0 + c) * NJ + j];
-      }
-      __syncthreads();
-      clearance_tile(&s_rb, sc, &s_mc, cfg, nc, ql, L);  // (ends with a barrier)
-      if (!edges) {
-        if (tid < nc) {
-          ClearDev o;
-          o.map = L.c_map[tid];
-          o.map_link = L.c_link[tid];
-          o.self = L.c_self[tid];
-          const int key = L.c_key[tid];
-          const bool has = cfg.with_self && key != INT_MAX;
-          o.self_a = has ? key >> 10 : -1;
-          o.self_b = has ? key & 1023 : -1;
-          o.pad = 0;
-          out_c[q0 + tid] = o;
+  // an edge's record and its running minima (wave 0, the same in all its lanes)
+  struct Done {
+    int e, M;
+    double r_map, r_self;
+    int r_mpt, r_mlink, r_spt, r_skey;
+  };
+  ticket_loop(
+      counter, (unsigned)n_items,
+      [&](unsigned slot) {
+        Done d{0, 0, cfg.D, HUGE_VAL, -1, -1, -1, -1};
+        long long q0 = 0;
+        if (edges) {
+          d.e = __builtin_amdgcn_readfirstlane(order[slot]);
+          d.M = __builtin_amdgcn_readfirstlane(edges[d.e].M);
+          if (tid < NJ) {
+            const double a = edges[d.e].a[tid], b = edges[d.e].b[tid];
+            ea[tid] = a;
+            es[tid] = edge_step(a, b, d.M);
+          }
+        } else {
+          q0 = (long long)slot * PASS_CT;
+          d.M = __builtin_amdgcn_readfirstlane((int)min((long long)PASS_CT, n - q0)) - 1;
         }
-      } else if (tid < 64) {
-        // the tile's least values and the lowest point attaining each; a later tile must be strictly below
-        double v = tid < nc ? L.c_map[tid] : HUGE_VAL;
-        int pt = tid < nc ? tid : INT_MAX;
-        wave_min_key(v, pt);
-        if (v < r_map) { r_map = v; r_mpt = base + pt; r_mlink = L.c_link[pt]; }
-        v = tid < nc ? L.c_self[tid] : HUGE_VAL;
-        pt = tid < nc ? tid : INT_MAX;
-        wave_min_key(v, pt);
-        if (v < r_self) { r_self = v; r_spt = base + pt; r_skey = L.c_key[pt]; }
-      }
-      __syncthreads();  // ql and the tile's results are rewritten by the next tile
-    }
-    // (every thread has read s_slot, ea and es: they passed the barriers above)
-    if (tid == 0) {
-      if (edges) {
+        __syncthreads();
+        for (int base = 0; base <= d.M; base += PASS_CT) {
+          const int nc = __builtin_amdgcn_readfirstlane(min(PASS_CT, d.M + 1 - base));
+          if (edges) {
+            edge_tile(ql, ea, es, base, nc);
+          } else {
+            for (int it = tid; it < nc * NJ; it += BLOCK) {
+              const int c = it / NJ, j = it - c * NJ;
+              ql[c][j] = q_rows[(q0 + c) * NJ + j];
+            }
+          }
+          __syncthreads();
+          clearance_tile(&s_rb, sc, &s_mc, cfg, nc, ql, L);  // (ends with a barrier)
+          if (!edges) {
+            if (tid < nc) {
+              ClearDev o;
+              o.map = L.c_map[tid];
+              o.map_link = L.c_link[tid];
+              o.self = L.c_self[tid];
+              const int key = L.c_key[tid];
+              const bool has = cfg.with_self && key != INT_MAX;
+              o.self_a = has ? key >> 10 : -1;
+              o.self_b = has ? key & 1023 : -1;
+              o.pad = 0;
+              out_c[q0 + tid] = o;
+            }
+          } else if (tid < 64) {
+            // the tile's least values and the lowest point attaining each; a later tile must be strictly below
+            double v = tid < nc ? L.c_map[tid] : HUGE_VAL;
+            int pt = tid < nc ? tid : INT_MAX;
+            wave_min_key(v, pt);
+            if (v < d.r_map) { d.r_map = v; d.r_mpt = base + pt; d.r_mlink = L.c_link[pt]; }
+            v = tid < nc ? L.c_self[tid] : HUGE_VAL;
+            pt = tid < nc ? tid : INT_MAX;
+            wave_min_key(v, pt);
+            if (v < d.r_self) { d.r_self = v; d.r_spt = base + pt; d.r_skey = L.c_key[pt]; }
+          }
+          __syncthreads();  // ql and the tile's results are rewritten by the next tile
+        }
+        return d;
+      },
+      [&](unsigned, const Done& d) {
+        if (!edges) return;
         EdgeClearDev o;
-        o.map = r_map; o.self = r_self;
-        o.map_point = r_mpt; o.self_point = r_spt;
-        o.map_link = r_mlink;
-        o.self_a = r_spt >= 0 ? r_skey >> 10 : -1;
-        o.self_b = r_spt >= 0 ? r_skey & 1023 : -1;
-        o.n_points = M + 1;
-        out_e[e] = o;
-      }
-      s_slot = atomicAdd(counter, 1u);
-    }
-    __syncthreads();
-    slot = (unsigned)__builtin_amdgcn_readfirstlane((int)s_slot);
-  }
+        o.map = d.r_map; o.self = d.r_self;
+        o.map_point = d.r_mpt; o.self_point = d.r_spt;
+        o.map_link = d.r_mlink;
+        o.self_a = d.r_spt >= 0 ? d.r_skey >> 10 : -1;
+        o.self_b = d.r_spt >= 0 ? d.r_skey & 1023 : -1;
+        o.n_points = d.M + 1;
+        out_e[d.e] = o;
+      });
 }
 
-size_t clearance_kernels_private_bytes() {
-  hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&clearance_kernel)) != hipSuccess) return 0;
-  return (size_t)fa.localSizeBytes;
-}
+size_t clearance_kernels_private_bytes() { return kernel_private_bytes(&clearance_kernel); }
 
 void launch_clearance(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const ClearCfg& cfg,
                       const double* q_rows, long long n, const EdgeDev* edges, const int* order, int n_items,

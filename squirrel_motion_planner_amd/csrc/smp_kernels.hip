@@ -15,7 +15,6 @@
 #include <vector>
 
 #include "smp_collide.h"
-#include "smp_edges.h"
 #include "smp_math.h"
 #include "smp_plan.h"
 #include "smp_types.h"
@@ -106,8 +105,7 @@ size_t check_kernels_private_bytes() {
                       reinterpret_cast<const void*>(&check_wide_kernel)};
   for (const void* k : ks)
     if (hipFuncGetAttributes(&fa, k) == hipSuccess && (size_t)fa.localSizeBytes > need) need = fa.localSizeBytes;
-  const size_t edges = edges_kernels_private_bytes();  // edges_kernel (smp_edges.hip) runs the same tiles
-  return edges > need ? edges : need;
+  return need;
 }
 
 void launch_check(int ct, int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const double* q,

@@ -11,11 +11,10 @@
 
 #include "../../include/smp_gpu.h"
 #include "smp_clearance.h"
-#include "smp_edges.h"
+#include "smp_pass.h"
 #include "smp_host.h"
 #include "smp_ik.h"
 #include "smp_plan.h"
-#include "smp_repair.h"
 #include "smp_types.h"
 
 struct smp_robot {

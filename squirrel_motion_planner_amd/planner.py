@@ -282,10 +282,7 @@ class GpuPlanner:
     def check_edges(self, frm, to, check_self=True, check_map=True):
         """Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule of smp_check_edges: (first_invalid,
         n_points) per edge frm[i] -> to[i]; first_invalid is the index of the first colliding point, -1 if free."""
-        a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
-        b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
-        if len(a) != len(b):
-            raise ValueError("check_edges: %d start and %d end configurations" % (len(a), len(b)))
+        a, b = _edge_rows("check_edges", frm, to)
         first = np.zeros(len(a), np.int64)
         npts = np.zeros(len(a), np.int32)
         check(lib().smp_check_edges(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(check_self),
@@ -303,25 +300,13 @@ class GpuPlanner:
         info = L.ShortcutInfo()
         rc = lib().smp_shortcut_path(self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map),
                                      int(window), ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
-        d = {f: getattr(info, f) for f, _ in L.ShortcutInfo._fields_}
-        if rc != L.SMP_OK:
-            err = L.SmpError(rc, "smp_shortcut_path")
-            err.info = d
-            raise err
-        try:
-            res = np.ctypeslib.as_array(out, shape=(n_out.value, 8)).copy()
-        finally:
-            lib().smp_buffer_free(out)
-        return res, d
+        return _returned_path("smp_shortcut_path", rc, out, n_out, info)
 
     def sample_detours(self, frm, to, samples, half_width, seed=1, round=0, check_self=True, check_map=True):
         """smp_sample_detours: for every gap frm[g] -> to[g], `samples` one-via detours drawn around the gap's centre
         within `half_width` and both legs of each checked densely, one launch.  Returns a dict of v (G, S, 8), M1, M2
         and free (G, S)."""
-        a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
-        b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
-        if len(a) != len(b):
-            raise ValueError("sample_detours: %d start and %d end configurations" % (len(a), len(b)))
+        a, b = _edge_rows("sample_detours", frm, to)
         n = len(a) * max(int(samples), 0)
         out = (L.Detour * max(n, 1))()
         check(lib().smp_sample_detours(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(samples),
@@ -345,16 +330,7 @@ class GpuPlanner:
         opts = L.RepairOpts(int(samples), int(rounds), int(seed))
         rc = lib().smp_repair_path(self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map),
                                    ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
-        d = {f: getattr(info, f) for f, _ in L.RepairInfo._fields_}
-        if rc != L.SMP_OK:
-            err = L.SmpError(rc, "smp_repair_path")
-            err.info = d
-            raise err
-        try:
-            res = np.ctypeslib.as_array(out, shape=(n_out.value, 8)).copy()
-        finally:
-            lib().smp_buffer_free(out)
-        return res, d
+        return _returned_path("smp_repair_path", rc, out, n_out, info)
 
     def clearance(self, q, max_dist=0.3, with_self=True, with_map=True):
         """smp_clearance_configs: distance of every configuration to the map (capped at max_dist) and to self-collision,
@@ -373,10 +349,7 @@ class GpuPlanner:
         """smp_clearance_edges: the minima of both clearances over every dense edge frm[i] -> to[i] (the density rule of
         smp_check_edges), the lowest points attaining them and those points' witness links, one launch.  Returns a
         structured array (EDGE_CLEARANCE_DTYPE); `clearance_info` keeps the call's point count and timing."""
-        a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
-        b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
-        if len(a) != len(b):
-            raise ValueError("edge_clearance: %d start and %d end configurations" % (len(a), len(b)))
+        a, b = _edge_rows("edge_clearance", frm, to)
         out = np.zeros(len(a), EDGE_CLEARANCE_DTYPE)
         info = L.ClearanceInfo()
         check(lib().smp_clearance_edges(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), float(max_dist),
@@ -605,6 +578,30 @@ EDGE_CLEARANCE_DTYPE = np.dtype([("map", np.float64), ("self", np.float64), ("ma
 IK_DEVIATION = [(-0.005, 0.005)] * 3 + [(-0.025, 0.025)] * 3
 
 _CALL_FAILURES = (L.SMP_ERR_HIP, L.SMP_ERR_NO_DEVICE, L.SMP_ERR_PARSE)
+
+
+def _edge_rows(what, frm, to):
+    """The contiguous (n, 8) start and end rows of a table of edges or gaps."""
+    a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
+    b = np.ascontiguousarray(np.asarray(to, np.float64).reshape(-1, 8))
+    if len(a) != len(b):
+        raise ValueError("%s: %d start and %d end configurations" % (what, len(a), len(b)))
+    return a, b
+
+
+def _returned_path(what, rc, out, n_out, info):
+    """(path (m, 8), info dict) of a call that hands back a path buffer, which is freed here; a failure raises SmpError
+    with the dict as its `info` attribute."""
+    d = {f: getattr(info, f) for f, _ in info._fields_}
+    if rc != L.SMP_OK:
+        err = L.SmpError(rc, what)
+        err.info = d
+        raise err
+    try:
+        res = np.ctypeslib.as_array(out, shape=(n_out.value, 8)).copy()
+    finally:
+        lib().smp_buffer_free(out)
+    return res, d
 
 
 def _result_dict(r):

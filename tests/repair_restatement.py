@@ -124,18 +124,43 @@ def repair(orc, w, samples=256, rounds=4, seed=1, self_=True, map_=True, n=R.N_S
         out["n_free"] += int(d["free"].sum())
         out["free_per_round"].append(int(d["free"].sum()))
         for t, g in enumerate(opened):
-            best = float("inf")
-            for s in range(samples):
-                if not d["free"][t, s]:
-                    continue
-                c = dist(a[t], d["v"][t, s]) + dist(d["v"][t, s], b[t])
-                if c < best:
-                    best, chosen[g], closed_round[g] = c, d["v"][t, s].copy(), rho
+            s = choose_detour(a[t], b[t], d["free"][t], d["v"][t])
+            if s >= 0:
+                chosen[g], closed_round[g] = d["v"][t, s].copy(), rho
     out.update(n_repaired=sum(c is not None for c in chosen), vias=chosen, closed_round=closed_round)
-    still = [g for g in range(len(gaps)) if chosen[g] is None]
-    if still:
-        out.update(status=ERR_NO_SOLUTION, first_blocked=gaps[still[0]][2])
+    e = first_open_gap(gaps, chosen)
+    if e >= 0:
+        out.update(status=ERR_NO_SOLUTION, first_blocked=e)
         return out
+    route, rows, cost_out = repaired_route(w, gaps, chosen, rb.rev, n, f)
+    out.update(path=rows, cost_out=cost_out, route=route)
+    return out
+
+
+def choose_detour(a, b, free, v):
+    """The sample a round chooses for the gap a -> b: the first strict minimum of dist(a, v) + dist(v, b) over the free
+    items, -1 if none is free."""
+    best, chosen = float("inf"), -1
+    for s in range(len(free)):
+        if not free[s]:
+            continue
+        c = dist(a, v[s]) + dist(v[s], b)
+        if c < best:
+            best, chosen = c, s
+    return chosen
+
+
+def first_open_gap(gaps, chosen):
+    """Step 4: the smallest blocked edge of the first gap without a via, -1 if every gap has one."""
+    for g in range(len(gaps)):
+        if chosen[g] is None:
+            return gaps[g][2]
+    return -1
+
+
+def repaired_route(w, gaps, chosen, rev, n, f):
+    """Step 5: (route, output rows, cost_out) of the path whose gaps are bridged by the vias chosen."""
+    k = len(w)
     route = []
     i, g = 0, 0
     while i < k:
@@ -147,7 +172,7 @@ def repair(orc, w, samples=256, rounds=4, seed=1, self_=True, map_=True, n=R.N_S
         else:
             i += 1
     route = np.array(route)
-    rm, rM = density(route[:-1], route[1:], rb.rev, n, f)
+    rm, rM = density(route[:-1], route[1:], rev, n, f)
     rows = []
     cost_out = 0.0
     for e in range(len(route) - 1):
@@ -156,8 +181,7 @@ def repair(orc, w, samples=256, rounds=4, seed=1, self_=True, map_=True, n=R.N_S
         rows.append(route[e])
         rows.extend(pts[n:int(rM[e]):n])
     rows.append(w[k - 1])
-    out.update(path=np.array(rows), cost_out=cost_out, route=route)
-    return out
+    return route, np.array(rows), cost_out
 
 
 # ------------------------------------------------------------------------------------------ shared inputs

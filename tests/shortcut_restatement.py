@@ -77,6 +77,13 @@ def shortcut(orc, w, rev, n, f, self_=True, map_=True, window=0):
     b = np.array([w[j] for _, j in pairs])
     m, M = density(a, b, rev, n, f)
     first = first_invalid(orc, a, b, M, self_, map_)
+    return shortcut_route(w, pairs, a, b, m, M, first, n)
+
+
+def shortcut_route(w, pairs, a, b, m, M, first, n):
+    """The part of shortcut that needs no oracle: the dynamic program over the candidates' first invalid points and
+    the rows of the route it finds."""
+    k = len(w)
     dp = [float("inf")] * k
     pred = [-1] * k
     pe = [-1] * k

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import clearance_restatement as C
+import gpu_info
 import shortcut_restatement as R
 from squirrel_motion_planner_amd import _lib as L
 from squirrel_motion_planner_amd.planner import GpuPlanner, Robot, Scene
@@ -117,6 +118,28 @@ def test_edges(gp, name):
     c0 = C.clearance(name, a[:1], D)
     assert one["map"][0] == c0["map"][0] and one["self"][0] == c0["self"][0]
     assert one["map_point"][0] == (0 if c0["map"][0] < D else -1) and one["self_point"][0] == 0
+
+
+def test_more_edges_than_workgroups(gp):
+    """A table of more edges than twice the CU count, so that every workgroup goes round the work loop more than once
+    (one workgroup per CU): a == b edges over the 97 cached poses, repeated.  Such an edge is 21 identical points, so its
+    minima and links are the pose's record and the lowest point attaining them is point 0."""
+    name, D = "c2", 0.3
+    cus = gpu_info.device_cus()
+    exp = C.expected(name, C.N_POSES, D)
+    idx = np.arange(2 * cus + 1) % C.N_POSES
+    q = C.poses(name)[idx]
+    assert len(q) > 2 * cus
+    use_scene(gp, name)
+    got = gp.edge_clearance(q, q, D)
+    print("CUs", cus, "edges", len(q), "kernel ms", gp.clearance_info["kernel_ms"])
+    for f in FIELDS:
+        bad = np.flatnonzero(got[f] != exp[f][idx])
+        assert len(bad) == 0, (f, bad[:8], got[f][bad[:8]], exp[f][idx][bad[:8]])
+    assert (got["n_points"] == R.N_SEG + 1).all()
+    assert np.array_equal(got["map_point"], np.where(exp["map"][idx] < D, 0, -1))
+    assert (got["self_point"] == 0).all()
+    assert gp.clearance_info["n_points"] == len(q) * (R.N_SEG + 1)
 
 
 def test_edges_flags_alone(gp):

@@ -4,6 +4,7 @@ count per edge, exactly."""
 import numpy as np
 import pytest
 
+import gpu_info
 import shortcut_restatement as R
 from squirrel_motion_planner_amd import _lib as L
 from squirrel_motion_planner_amd.planner import GpuPlanner, Robot, Scene
@@ -136,6 +137,29 @@ def test_edge_cases(gp, robot):
     assert e.value.status == L.SMP_ERR_ARG
     first, _ = bare.check_edges([start], [goal], check_map=False)
     assert first.tolist() == R.first_invalid(R.oracle_for("c2"), [start], [goal], Mg, True, False).tolist()
+
+
+def test_more_edges_than_workgroups(gp):
+    """A table of more edges than twice the CU count, so that every workgroup goes round the work loop more than once
+    (one workgroup per CU): the 64 long edges of C2, then a == b edges of random configurations, 21 points each, whose
+    answer is check_configs' of that configuration (test_edge_cases).  The expectation is the oracle's alone."""
+    name = "c2"
+    cus = gpu_info.device_cus()
+    sc = use_scene(gp, name)
+    la, lb = R.long_edges(name)
+    q = R.random_configs(sc, 2 * cus + 1, 11)
+    a, b = np.concatenate([la, q]), np.concatenate([lb, q])
+    assert len(a) > 2 * cus
+    orc = R.oracle_for(name)
+    _, M = R.density(la, lb, R.orobot().rev, R.N_SEG, R.STEP)
+    v = orc.check_configs(q)
+    assert 0 < v.sum() < len(v)
+    want = np.concatenate([R.first_invalid(orc, la, lb, M), np.where(v, -1, 0)])
+    want_pts = np.concatenate([M + 1, np.full(len(q), R.N_SEG + 1)])
+    first, npts = gp.check_edges(a, b)
+    print("CUs", cus, "edges", len(a), "valid configurations", int(v.sum()), "of", len(v))
+    assert np.array_equal(npts, want_pts)
+    assert np.array_equal(first, want)
 
 
 def test_deterministic(gp):
