@@ -172,6 +172,8 @@ typedef struct smp_stats {
   double time_first_solution_host; /* seconds from smp_plan entry until the host saw the first feasible path (host
                                     clock: start / goal checks, allocation, uploads and launch included; SURVEY 8d
                                     counts from run_planner entry, birrt_star.cpp:1075-1081); -1 if none */
+  int64_t scout_conn_row_hits;   /* connects whose nearest node's row came from the scout's connect record */
+  int64_t scout_conn_batch_hits; /* connects whose near candidates' rows came from the scout's connect record */
 } smp_stats;
 
 typedef struct smp_result {

@@ -578,6 +578,8 @@ static int plan_assemble(PlanCall& c, smp_result* out, std::vector<char>& done) 
     st.scout_near_hits = s.sc_near;
     st.scout_edge_hits = s.sc_edge_hit;
     st.scout_edge_misses = s.sc_edge_miss;
+    st.scout_conn_row_hits = s.sc_conn_row;
+    st.scout_conn_batch_hits = s.sc_conn_batch;
     st.scout_wait_seconds = (double)s.sc_wait / p->wall_rate_hz;
     for (int k = 0; k < 32; ++k) {
       const bool count = k == 8 || k == 11 || (k >= 20 && k < 28) || k == 30;

@@ -385,6 +385,13 @@ struct PlanLds {
   double eg_base[MAXE][3], eg_cost[MAXE][3];
   double eg_acc[MAXE][3];             // edge_costs: the segment-norm sums (eg_cost = eg_base + eg_acc)
   int eg_first[MAXE], eg_need[MAXE], eg_near[MAXE], eg_ptr[MAXE];
+  // leader, choose-parent's and connect's candidate batches: the parent of the tree node edge e starts from (eg_near[e]),
+  // so that with eg_start[e] and eg_base[e] the batch holds the node's whole row (cur_from_batch)
+  int eg_par[MAXE];
+  // leader, connect: the direct edge is needed (eg_need[0] as connect's entry formed it), in a word of its own: every
+  // wave branches on it behind the entry's barrier, and when the edge is not needed no barrier lies between that read
+  // and the near part's fill of eg_need[0 ..]; this word's next writer is the next connect's entry
+  int conn_need0;
   int rw_par[MAXE], rw_next;          // rewire: candidates' parents (refreshed after every commit), resume point
   double rw_cost[MAXE][3];            // rewire: candidates' costs
   int tile_e[PLAN_CT], tile_i[PLAN_CT], tile_n;
@@ -430,6 +437,7 @@ struct PlanLds {
   int trole;                    // SMP_TRACE builds: 0 leader, 1 / 2 scout (trace records of this workgroup)
   unsigned tn;                  // records of this role so far
   long long tit;                // iteration the records belong to
+  int tbar;                     // __syncthreads() executed by this workgroup since its iteration / pass began
 #endif
   int sp_on, sp_stage, sp_go[2];
   double fnn_d;                 // near_set<K, true>: the nearest node of the same configuration (distance, id)
@@ -442,7 +450,6 @@ struct PlanLds {
   int asked[SCOUT_SLOTS];       // leader: scout s + 1 asked for iteration k in slot k % SCOUT_SLOTS, 0 = none
   int asked_conn[SCOUT_SLOTS];  // leader: that record will carry connect's scans (stage SC_CONN)
   int asked_pre[SCOUT_SLOTS];   // leader: asked before the first solution (a pre-solution record)
-  int conn_rec;                 // leader: connect of this iteration takes its scans from the record (g_L.sr.cc)
   int two_scouts;               // scout: two scouts share the iterations (post-solution records get SC_CONN)
   unsigned sc_mod;              // scout: rewire commits of its pass's tree when the pass read it (stage granules carry it)
   unsigned rw_at0;              // leader: rewire commits of tree_A at the start of the iteration (records must match)
@@ -496,8 +503,24 @@ __device__ unsigned g_tlog_n[4];
         ((unsigned long long)(__LINE__ & 0x3fff) << 40) | (wall_clock64() & 0xffffffffffull);                  \
     g_tlog_n[g_L.trole] = ++g_L.tn;                                                                            \
   }
+// The barriers of a leader iteration, counted by thread 0 (every __syncthreads() below this line) and logged at the
+// iteration's end as a record whose line field is TR_BAR0 + the count (trace_probe.py prints them apart).
+constexpr int TR_BAR0 = 16000;
+#define __syncthreads()                 \
+  do {                                  \
+    if (threadIdx.x == 0) ++g_L.tbar;   \
+    __syncthreads();                    \
+  } while (0)
+#define TR_BARRIERS()                                                                                          \
+  if (threadIdx.x == 0 && g_L.tit >= SMP_TRACE_IT0 && g_L.tit < SMP_TRACE_IT1 && g_L.tn < TLOG_ROLE) {        \
+    g_tlog[g_L.trole * TLOG_ROLE + g_L.tn] =                                                                   \
+        ((unsigned long long)g_L.trole << 62) | ((unsigned long long)((g_L.tit - SMP_TRACE_IT0) & 0xff) << 54) | \
+        ((unsigned long long)((TR_BAR0 + min(g_L.tbar, 383)) & 0x3fff) << 40) | (wall_clock64() & 0xffffffffffull); \
+    g_tlog_n[g_L.trole] = ++g_L.tn;                                                                            \
+  }
 #else
 #define TR()
+#define TR_BARRIERS()
 #endif
 
 // Phase clocks (thread 0, s_memrealtime ticks): where an iteration spends its time.
@@ -870,6 +893,7 @@ __device__ __forceinline__ int nearest_leader(const Ctx& C, int t, const double*
     if (uni(R.ok && R.t == t && R.X <= n && same8(q, R.q))) {
       if (threadIdx.x == 0) g_L.S.sc_nn++;
       if (uni(R.X < n)) {
+        TR();
         double dp;
         const int ip = uni(n - R.X <= 64) ? tail_scan(C, t, q, R.X, n, &dp) : nearest_scan_call(C, t, q, R.X, &dp);
         if (dp < R.d) return ip;
@@ -3297,6 +3321,14 @@ static_assert(sizeof(ScoutNN) % 8 == 0 && sizeof(ScoutNear) % 8 == 0 && sizeof(S
               "scout record sections are 8-byte words");
 
 constexpr unsigned long long SCOUT_WAIT = 6000;  // device-clock ticks (60 us) the leader waits for one scout stage
+// ... and for connect's scans (stage SC_CONN) before it runs them itself.  A scout starts them when its main pass is
+// done, so a late pass delivers them 12-16 us after the rewire record the leader has just taken; a leader that gave up
+// after 10 us (the limit up to round 11) then ran both scans itself, about 13 us more, beside the scout's.  20 us
+// covers the scout's scans (C2, builds taking turns: 10 us 4.85, 20 us 4.96, 30 us 4.95-4.98, 40 us 4.95 M configs/s,
+// DESIGN.md §5 "Round 12").  A scout that is not on the iteration, or has left, ends the wait at once as before.
+#ifndef SMP_CONN_WAIT
+#define SMP_CONN_WAIT 2000
+#endif
 
 // Leader: waits until the scout's record of this iteration reached stage s (or the scout is not working on this
 // iteration, or SCOUT_WAIT passes: then the scout is not asked again this iteration) and copies the sections of
@@ -3341,6 +3373,7 @@ __device__ bool spec_stage(const Ctx& C, int s, unsigned long long wait) {
     return false;
   }
   spec_copy(sb, par, have, got - 1);  // stages (have, st] arrived
+  TR();
   return true;
 }
 
@@ -3535,6 +3568,7 @@ __device__ void scout_request_ahead2(const Ctx& C, int tA) {
   if (C.Q.nscouts < 2) return;
   drain();
   __syncthreads();
+  TR();
   if (threadIdx.x == 0) {
     const long long j = g_L.S.iter, k = j + 2;
     bool fenced = false;
@@ -4541,6 +4575,18 @@ __device__ __forceinline__ int choose_prefix() {
   const bool below = lane < m && g_L.lo_c[lane] < g_L.xn.c[0];
   return min(m, (int)__builtin_ctzll(~__ballot(below)));  // (m <= 20: lane 63 is never `below`)
 }
+// Thread 0: g_L.cur = the tree node that edge e of choose-parent's / connect's candidate batch starts from, out of the
+// batch's own rows (eg_start, eg_base, eg_near, eg_par: the node's row as loaded, or as the record carried it, when the
+// batch was filled).  Nothing writes the tree between the fill and the chain that starts from the node -- edge costs,
+// validity jobs and the scans under them only read it, the pending via nodes are inserted after the last chain -- and
+// a chain rewrites edge slot 0 only, after the row of the edge it starts from was taken (connect's later edges have
+// e >= 1): the same words load_node would fetch, without the memory round trip on thread 0.
+__device__ __forceinline__ void cur_from_batch(int e) {
+  for (int j = 0; j < NJ; ++j) g_L.cur.q[j] = g_L.eg_start[e][j];
+  for (int k = 0; k < 3; ++k) g_L.cur.c[k] = g_L.eg_base[e][k];
+  g_L.cur.id = g_L.eg_near[e];
+  g_L.cur.parent = g_L.eg_par[e];
+}
 __device__ void choose_parent(const Ctx& C, int t) {
   if (threadIdx.x < 64) {
     const int E = choose_prefix();  // candidate prefix: stop at the first near node whose cost is not below x_new's
@@ -4552,6 +4598,7 @@ __device__ void choose_parent(const Ctx& C, int t) {
     }
   }
   __syncthreads();
+  TR();
   const int E = uni(g_L.cnt);
   if (E > 0) {
     if (threadIdx.x < E) {
@@ -4561,24 +4608,30 @@ __device__ void choose_parent(const Ctx& C, int t) {
       for (int j = 0; j < NJ; ++j) { g_L.eg_start[e][j] = nd.q[j]; g_L.eg_target[e][j] = g_L.xn.q[j]; }
       for (int k = 0; k < 3; ++k) g_L.eg_base[e][k] = nd.c[k];
       g_L.eg_near[e] = nd.id;
+      g_L.eg_par[e] = nd.parent;
     }
     __syncthreads();
+    TR();
     if (C.Q.jb && rec_match(C, E, SC_CHOOSE)) edge_costs_rec(E);
     else edge_costs(C, E);
+    TR();
     if (threadIdx.x < E) g_L.eg_need[threadIdx.x] = g_L.eg_cost[threadIdx.x][0] <= g_L.xn.c[0];
     for (int e = E + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
     __syncthreads();
     edge_validity(C, E, true, P_XCHOOSE, 0, 0, SC_CHOOSE);
+    TR();
     count_edges(E, true);  // -> g_L.found
+    TR();
     if (threadIdx.x == 0) {
       if (g_L.found >= 0) {
         g_L.ext_bp = 1;
         g_L.n_via = 0;
         g_L.nn_t = g_L.S.n[t];
-        load_node(C, t, g_L.eg_near[g_L.found], &g_L.cur);
+        cur_from_batch(g_L.found);
       }
     }
     __syncthreads();
+    TR();
     if (uni(g_L.found) >= 0) {
       via_chain(C, g_L.xn.q);
       if (threadIdx.x == 0) {
@@ -4624,6 +4677,7 @@ __device__ void rewire(const Ctx& C, int t) {
   const int cap = g_L.S.cap;
   const TreeDev& T = C.Q.tr[t];
   rewire_count(T);
+  TR();
   const int cnt = uni(g_L.cnt);
   if (cnt == 0) return;
   // candidates k = n-1 .. n-cnt  ->  edge slot e = n-1-k
@@ -4638,8 +4692,10 @@ __device__ void rewire(const Ctx& C, int t) {
     g_L.eg_near[e] = v;
   }
   __syncthreads();
+  TR();
   if (C.Q.jb && rec_match(C, cnt, SC_DONE)) edge_costs_rec(cnt);
   else edge_costs(C, cnt);
+  TR();
   if (threadIdx.x == 0 && g_L.sp_on) scout_ask_early(C, g_L.sp_stage);  // before this iteration's commits
   if (threadIdx.x < cnt) {
     int e = threadIdx.x, v = g_L.eg_near[e];
@@ -4650,6 +4706,7 @@ __device__ void rewire(const Ctx& C, int t) {
   }
   for (int e = cnt + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
   __syncthreads();
+  TR();
   edge_validity(C, cnt, false, P_XREWIRE, OV_NN, 1 - t, SC_DONE);
   TR();
   DETAIL_BEGIN(_dr);
@@ -4752,28 +4809,80 @@ __device__ void rewire(const Ctx& C, int t) {
 // connectGraphsInterpolation, unconstrained branch + commit (birrt_star.cpp:2608-3046, 3219-3288).
 // t = tree_B; g_L.xc = its nearest node to x_new; g_L.xn = x_new (node of the other tree).
 __device__ void connect_tail(const Ctx& C, int t);
-__device__ void connect_graphs(const Ctx& C, int t) {
-  if (threadIdx.x == 0) {
-    g_L.tree_expand = 0;
-    g_L.best_nv = 10000.0;
-    g_L.n_via = 0;
-    for (int k = 0; k < 3; ++k) g_L.csp[k] = g_L.S.cbest[k];
-    for (int j = 0; j < NJ; ++j) { g_L.eg_start[0][j] = g_L.xc.q[j]; g_L.eg_target[0][j] = g_L.xn.q[j]; }
-    for (int k = 0; k < 3; ++k) g_L.eg_base[0][k] = g_L.xc.c[k];
-    g_L.sel.id = -1;
+// crec: connect takes its scans from the iteration's SC_CONN record (conn_stage).  xrow: the record also holds the
+// nearest node's row (ScoutConn::xq ..) and that node is connect's (the caller compared the ids): g_L.xc and the direct
+// edge are filled from the record here; else the caller has loaded g_L.xc.
+__device__ void connect_graphs(const Ctx& C, int t, bool crec = false, bool xrow = false) {
+  if (xrow) {
+    // The direct edge nearest -> x_new wholly from LDS, in one step: the row the scout read over the same final tree_B
+    // (the record was taken for this tree size, configuration and excluded id; nothing writes tree_B between the
+    // leader's hand-over of it and this connect), the interpolation step and end as edge_costs_acc forms them, the
+    // record's sums, the solution cost and the need flag as the thread-0 sections below form them (the same
+    // operations in the same order), each on the lane that holds its inputs.  No barrier is needed before it: the
+    // record's words were in LDS before spec_copy's barriers, g_L.xn is final since the rewire step, and the
+    // last readers of the fields written here (the rewire batch's edge rows, take_spec's g_L.spec) are behind
+    // take_spec's barriers in the caller.  One barrier after it instead of five, and no load of the row.
+    const ScoutConn& R = g_L.sr.cc;
+    const int np = g_L.S.n_pts;
+    if (threadIdx.x < NJ) {
+      const int j = threadIdx.x;
+      const double s0 = R.xq[j], g0 = g_L.xn.q[j];
+      const double st = (g0 - s0) / double(np);
+      g_L.xc.q[j] = s0;
+      g_L.eg_start[0][j] = s0;
+      g_L.eg_target[0][j] = g0;
+      g_L.eg_step[0][j] = st;
+      g_L.eg_end[0][j] = s0 + np * st;
+    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + 3) {
+      const int k = threadIdx.x - 64;
+      const double b = R.xcost[k], a = R.acc0[k];
+      const double c = b + a, so = c + g_L.xn.c[k], cb = g_L.S.cbest[k];
+      g_L.xc.c[k] = b;
+      g_L.eg_base[0][k] = b;
+      g_L.eg_acc[0][k] = a;
+      g_L.eg_cost[0][k] = c;
+      g_L.sol[k] = so;
+      g_L.csp[k] = cb;
+      if (k == 0) { g_L.eg_need[0] = so < cb; g_L.conn_need0 = so < cb; }
+    } else if (threadIdx.x == 128) {
+      g_L.xc.id = R.d < 10000.0 ? R.id : 0;
+      g_L.xc.parent = R.xparent;
+      g_L.tree_expand = 0;
+      g_L.best_nv = 10000.0;
+      g_L.n_via = 0;
+      g_L.sel.id = -1;
+      g_L.spec = OV_NONE;
+      g_L.S.sc_conn_row++;
+    }
+    __syncthreads();
+    TR();
+  } else {
+    if (threadIdx.x == 0) {
+      g_L.tree_expand = 0;
+      g_L.best_nv = 10000.0;
+      g_L.n_via = 0;
+      for (int k = 0; k < 3; ++k) g_L.csp[k] = g_L.S.cbest[k];
+      for (int j = 0; j < NJ; ++j) { g_L.eg_start[0][j] = g_L.xc.q[j]; g_L.eg_target[0][j] = g_L.xn.q[j]; }
+      for (int k = 0; k < 3; ++k) g_L.eg_base[0][k] = g_L.xc.c[k];
+      g_L.sel.id = -1;
+    }
+    __syncthreads();
+    TR();
+    if (crec) edge_costs_acc(1, (const double (*)[3])g_L.sr.cc.acc0);
+    else edge_costs(C, 1);
+    TR();
+    if (threadIdx.x == 0) {
+      for (int k = 0; k < 3; ++k) g_L.sol[k] = g_L.eg_cost[0][k] + g_L.xn.c[k];
+      g_L.eg_need[0] = g_L.sol[0] < g_L.csp[0];
+      g_L.conn_need0 = g_L.eg_need[0];
+      // (with the need flag, under one barrier: g_L.spec was last read by the caller's take_spec, behind its barriers and
+      // the one above; edge_costs does not touch it, and its next reader is behind the barrier below)
+      g_L.spec = OV_NONE;
+    }
+    __syncthreads();
+    TR();
   }
-  __syncthreads();
-  const bool crec = uni(g_L.conn_rec) != 0;
-  if (crec) edge_costs_acc(1, (const double (*)[3])g_L.sr.cc.acc0);
-  else edge_costs(C, 1);
-  if (threadIdx.x == 0) {
-    for (int k = 0; k < 3; ++k) g_L.sol[k] = g_L.eg_cost[0][k] + g_L.xn.c[k];
-    g_L.eg_need[0] = g_L.sol[0] < g_L.csp[0];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) g_L.spec = OV_NONE;
-  __syncthreads();
-  if (uni(g_L.eg_need[0])) {
+  if (uni(g_L.conn_need0)) {  // (not eg_need[0]: see conn_need0)
     if (uni(!g_L.S.have_sol && g_L.sp_on && g_L.sp_stage >= SC_DONE && g_L.sr.cn.ok && g_L.sr.cn.t == t &&
             same8(g_L.sr.cn.e.s, g_L.eg_start[0]) && same8(g_L.sr.cn.e.g, g_L.eg_target[0]))) {
       // the scout checked this edge (before the first solution: no near set to overlap)
@@ -4787,6 +4896,7 @@ __device__ void connect_graphs(const Ctx& C, int t) {
     } else {
       edge_validity(C, 1, false, P_XCONNECT, (g_L.S.have_sol && !crec) ? OV_NEAR_XN : OV_NONE, t);
     }
+    TR();
     if (threadIdx.x == 0) {
       int f = g_L.eg_first[0];
       count_edge(f);
@@ -4815,7 +4925,65 @@ __device__ void connect_graphs(const Ctx& C, int t) {
     }
     __syncthreads();
   }
+  TR();
   if (uni(g_L.S.have_sol)) {
+    // rrow: the record holds the rows of all of connect's near candidates (ScoutConn::rq ..: lo_i[e], e < nrow)
+    const bool rrow = crec && uni(g_L.sr.cc.nrow >= 0 && g_L.sr.cc.nrow <= CONN_ROWS &&
+                                  g_L.sr.cc.nrow == min(g_L.sr.cc.n_lo, g_L.S.max_near));
+    int E;
+    if (rrow) {
+      // The near set, the candidate batch (rows, interpolation steps, the record's sums) and the need flags in one step
+      // from the record, each word on a thread of its own: what the steps below do from the lists and the loaded rows,
+      // the same operations in the same order (eg_cost = base + sum; need = lo_c < x_new's cost && eg_cost + x_new's
+      // cost < csp).  g_L.spec is OV_NONE here (a connect with a record runs its direct edge without overlap work), so
+      // take_spec would answer no.  Readers of the fields written: behind the barrier; their last writers (the direct
+      // edge's chain: slot 0, csp) are before the barrier above.  Their last readers: when the direct edge was needed,
+      // before the barrier that ends its block; when it was not, no barrier lies between the entry's and this step, and
+      // all a wave reads of LDS in between is conn_need0, have_sol, max_near and the record (crec, rrow), none of which
+      // is written here -- which is why the branch above reads conn_need0 and not eg_need[0].
+      const ScoutConn& R = g_L.sr.cc;
+      E = uni(R.nrow);
+      const int np = g_L.S.n_pts;
+      const int x = threadIdx.x;
+      if (x < E * NJ) {
+        const int e = x / NJ, j = x - e * NJ;
+        const double s0 = R.rq[e][j], g0 = g_L.xn.q[j];
+        const double st = (g0 - s0) / double(np);
+        g_L.eg_start[e][j] = s0;
+        g_L.eg_target[e][j] = g0;
+        g_L.eg_step[e][j] = st;
+        g_L.eg_end[e][j] = s0 + np * st;
+      } else if (x >= 192 && x < 192 + E * 3) {
+        const int i = x - 192, e = i / 3, k = i - e * 3;
+        const double b = R.rcost[e][k], a = R.acc[e][k];
+        g_L.eg_base[e][k] = b;
+        g_L.eg_acc[e][k] = a;
+        g_L.eg_cost[e][k] = b + a;
+      } else if (x >= 256 && x < 256 + MAXE) {
+        const int e = x - 256;
+        int need = 0;
+        if (e < E) {
+          g_L.eg_near[e] = R.lo_i[e];
+          g_L.eg_par[e] = R.rparent[e];
+          const double c0 = R.rcost[e][0] + R.acc[e][0];
+          const double s0 = c0 + g_L.xn.c[0];
+          need = (R.lo_c[e] < g_L.xn.c[0]) && (s0 < g_L.csp[0]);
+        }
+        g_L.eg_need[e] = need;
+      } else if (x >= 320 && x < 320 + MAX_NEAR) {
+        const int i = x - 320;
+        g_L.lo_i[i] = R.lo_i[i]; g_L.lo_c[i] = R.lo_c[i];
+        g_L.hi_i[i] = R.hi_i[i]; g_L.hi_c[i] = R.hi_c[i];
+      } else if (x == 384) {
+        g_L.nk = R.nk; g_L.n_lo = R.n_lo; g_L.n_hi = R.n_hi;
+        g_L.cnt = E;
+        g_L.S.near_nodes += g_L.S.n[t];
+        g_L.S.sc_near++;
+        g_L.S.sc_conn_batch++;
+      }
+      __syncthreads();
+      TR();
+    } else {
     if (!take_spec(OV_NEAR_XN)) {
       if (crec) {  // the record's near set of x_new over the same final tree
         const ScoutConn& R = g_L.sr.cc;
@@ -4838,7 +5006,8 @@ __device__ void connect_graphs(const Ctx& C, int t) {
       g_L.cnt = m;
     }
     __syncthreads();
-    const int E = uni(g_L.cnt);
+    TR();
+    E = uni(g_L.cnt);
     if (E > 0) {
       if (threadIdx.x < E) {
         int e = threadIdx.x;
@@ -4847,10 +5016,13 @@ __device__ void connect_graphs(const Ctx& C, int t) {
         for (int j = 0; j < NJ; ++j) { g_L.eg_start[e][j] = nd.q[j]; g_L.eg_target[e][j] = g_L.xn.q[j]; }
         for (int k = 0; k < 3; ++k) g_L.eg_base[e][k] = nd.c[k];
         g_L.eg_near[e] = nd.id;
+        g_L.eg_par[e] = nd.parent;
       }
       __syncthreads();
+      TR();
       if (crec) edge_costs_acc(E, g_L.sr.cc.acc);
       else edge_costs(C, E);
+      TR();
       if (threadIdx.x < E) {
         int e = threadIdx.x;
         double s0 = g_L.eg_cost[e][0] + g_L.xn.c[0];
@@ -4858,6 +5030,9 @@ __device__ void connect_graphs(const Ctx& C, int t) {
       }
       for (int e = E + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
       __syncthreads();
+    }
+    }
+    if (E > 0) {
       if (crec && uni(g_L.sr.cc.nfirst >= E)) {  // the record's candidates, checked to the end (scout_connect)
         if (threadIdx.x < 64) {  // (E <= max_near <= 20: wave 0)
           if ((int)threadIdx.x < E) g_L.eg_first[threadIdx.x] = g_L.sr.cc.first[threadIdx.x];
@@ -4868,6 +5043,7 @@ __device__ void connect_graphs(const Ctx& C, int t) {
       } else {
         edge_validity(C, E, true, P_XCONNECT);
       }
+      TR();
       DETAIL_BEGIN(_dn);
       // replay of the near loop (birrt_star.cpp:2820-3030).  An edge acts (connects: 1, extends: 2) only on
       // conditions of state that changes when an edge acts, so wave 0 evaluates every remaining edge against
@@ -4912,11 +5088,12 @@ __device__ void connect_graphs(const Ctx& C, int t) {
               }
               g_L.n_via = 0;
               g_L.nn_t = g_L.S.n[t];
-              load_node(C, t, g_L.eg_near[ev], &g_L.cur);
+              cur_from_batch(ev);
             }
           }
         }
         __syncthreads();
+        TR();
         const int flag_e = uni(g_L.flag);
         if (flag_e == 0) break;
         if (flag_e == 1) {
@@ -4935,6 +5112,7 @@ __device__ void connect_graphs(const Ctx& C, int t) {
   }
   insert_via(C, t);
   connect_tail(C, t);
+  TR();
 }
 
 // connectGraphs' commit (birrt_star.cpp:3219-3288), after the via nodes are inserted: the connection node on a
@@ -4964,18 +5142,16 @@ __device__ void connect_tail(const Ctx& C, int t) {
 }
 
 // Leader, connect step of an iteration after the first solution: takes connect's scans from the scout's record
-// (stage SC_CONN) if it is there within 10 us and was made for this x_new over the final tree_B (same size, same
-// configuration, same excluded id) -> g_L.conn_rec.  All threads.
+// (stage SC_CONN) if it is there within SMP_CONN_WAIT and was made for this x_new over the final tree_B (same size, same
+// configuration, same excluded id).  All threads; the answer is block-uniform and goes to connect_graphs as an
+// argument.  No barrier of its own: it writes nothing, asked_conn was written at the iteration's start, the record's
+// words are behind spec_copy's barriers, and S.n[B] / g_L.xn are final since the rewire step's last barrier.
 __device__ bool conn_stage(const Ctx& C, int B) {
-  if (threadIdx.x == 0) g_L.conn_rec = 0;
-  __syncthreads();
+  TR();
   if (!uni(g_L.asked_conn[g_L.S.iter & (SCOUT_SLOTS - 1)])) return false;
-  if (!spec_stage(C, SC_CONN, 1000)) return false;
+  if (!spec_stage(C, SC_CONN, SMP_CONN_WAIT)) return false;
   const ScoutConn& R = g_L.sr.cc;
-  const bool ok = uni(R.ok && R.t == B && R.X == g_L.S.n[B] && R.excl == g_L.xn.id && same8(R.q, g_L.xn.q));
-  if (ok && threadIdx.x == 0) g_L.conn_rec = 1;
-  __syncthreads();
-  return ok;
+  return uni(R.ok && R.t == B && R.X == g_L.S.n[B] && R.excl == g_L.xn.id && same8(R.q, g_L.xn.q)) != 0;
 }
 
 // Leader, an iteration before the first solution committed from its complete scout record (DESIGN.md "Pre-solution
@@ -5259,9 +5435,8 @@ __device__ __forceinline__ void iteration(const Ctx& C) {
   const int A = uni(g_L.S.A), B = 1 - A;
   unsigned long long _t0 = threadIdx.x == 0 ? pclk() : 0, _t1;
 #ifdef SMP_TRACE
-  if (threadIdx.x == 0) g_L.tit = g_L.S.iter;
+  if (threadIdx.x == 0) { g_L.tit = g_L.S.iter; g_L.tbar = 0; }
 #endif
-  if (threadIdx.x == 0) g_L.conn_rec = 0;
   TR();
 #define PHASE(k) if (threadIdx.x == 0) { _t1 = pclk(); g_L.S.prof[k] += _t1 - _t0; _t0 = _t1; }
   // two waves in parallel (disjoint LDS fields; each a serial chain of LDS reads)
@@ -5355,19 +5530,25 @@ __device__ __forceinline__ void iteration(const Ctx& C) {
     PHASE(P_CHOOSE);
   }
   if (uni(g_L.ext_nn || g_L.ext_bp)) {
-    if (threadIdx.x == 0) insert_node(C, A, g_L.en_start, g_L.en_target, g_L.xn);
-    __syncthreads();
-    if (threadIdx.x == 0) g_L.spec = OV_NONE;
+    TR();
+    // (g_L.spec under the insert's barrier: its last readers, take_spec before the near set and the expand job's
+    // overlap work, are behind the barriers that end those steps; its next ones are behind the barrier below)
+    if (threadIdx.x == 0) {
+      insert_node(C, A, g_L.en_start, g_L.en_target, g_L.xn);
+      g_L.spec = OV_NONE;
+    }
     __syncthreads();
     TR();
     if (opt) {
       rewire(C, A);
+      TR();
       scout_request_ahead2(C, A);
     }
     TR();
     PHASE(P_REWIRE);
     int cid;
     const bool crec = opt && conn_stage(C, B);
+    TR();
     if (take_spec(OV_NN)) {
       cid = uni(g_L.spec_nn);
     } else if (crec) {
@@ -5387,11 +5568,17 @@ __device__ __forceinline__ void iteration(const Ctx& C) {
     } else {
       cid = nearest(C, B, g_L.xn.q);
     }
-    if (threadIdx.x == 0) load_node(C, B, cid, &g_L.xc);
-    __syncthreads();
+    TR();
+    // with a connect record whose nearest node is connect's (always, unless the rewire job's overlap scan answered:
+    // then the ids are compared) its row comes from the record, inside connect_graphs
+    const bool xrow = crec && uni(g_L.sr.cc.nrow >= 0) && cid == uni(g_L.sr.cc.d < 10000.0 ? g_L.sr.cc.id : 0);
+    if (!xrow) {
+      if (threadIdx.x == 0) load_node(C, B, cid, &g_L.xc);
+      __syncthreads();
+    }
     TR();
     PHASE(P_NN);
-    connect_graphs(C, B);
+    connect_graphs(C, B, crec, xrow);
     TR();
     PHASE(P_CONNECT);
   }
@@ -5423,6 +5610,7 @@ __device__ __forceinline__ void iteration(const Ctx& C) {
     }
   }
   __syncthreads();
+  TR_BARRIERS();
 }
 
 // ----------------------------------------------------------------------------------------------- scout
@@ -5517,6 +5705,11 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
     load_node(C, tb, g_L.lo_i[e], &nd);
     for (int j = 0; j < NJ; ++j) { g_L.eg_start[1 + e][j] = nd.q[j]; g_L.eg_target[1 + e][j] = g_L.xn.q[j]; }
     for (int k = 0; k < 3; ++k) g_L.eg_base[1 + e][k] = 0.0;
+    if (e < CONN_ROWS) {  // the row as read, for the leader's connect (ScoutConn::rq)
+      for (int j = 0; j < NJ; ++j) R.cc.rq[e][j] = nd.q[j];
+      for (int k = 0; k < 3; ++k) R.cc.rcost[e][k] = nd.c[k];
+      R.cc.rparent[e] = nd.parent;
+    }
   }
   __syncthreads();
   edge_costs(C, 1 + E);
@@ -5545,6 +5738,10 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
     for (int k = 0; k < 3; ++k) R.cc.acc0[k] = g_L.eg_acc[0][k];
     R.cc.X = g_L.S.n[tb]; R.cc.t = tb; R.cc.excl = g_L.xn.id;
     R.cc.nk = g_L.nk; R.cc.n_lo = g_L.n_lo; R.cc.n_hi = g_L.n_hi;
+    for (int j = 0; j < NJ; ++j) R.cc.xq[j] = g_L.xc.q[j];
+    for (int k = 0; k < 3; ++k) R.cc.xcost[k] = g_L.xc.c[k];
+    R.cc.xparent = g_L.xc.parent;
+    R.cc.nrow = E <= CONN_ROWS ? E : -1;
     R.cc.ok = 1;
   }
   __syncthreads();
@@ -6415,7 +6612,6 @@ __global__ void __launch_bounds__(BLOCK) plan_kernel(const RobotDev* __restrict_
     g_L.sc_seen = 0;
     g_L.sc_dead = 0;
     for (int k = 0; k < SCOUT_SLOTS; ++k) { g_L.asked[k] = 0; g_L.asked_conn[k] = 0; g_L.asked_pre[k] = 0; }
-    g_L.conn_rec = 0;
     g_L.rec_grp = -1;
     g_L.count_slot = 0;
     g_L.job_seq = 0;

@@ -47,6 +47,7 @@ struct QState {                // per query, persisted in global memory across l
   long long nn_nodes, near_nodes;  // nodes streamed by nearest / near scans (algorithmic bytes)
   long long smp_hits;              // samples taken from the run-ahead sampler
   long long sc_nn, sc_near, sc_edge_hit, sc_edge_miss;  // scout results used: nearest, near sets, edges (+ misses)
+  long long sc_conn_row, sc_conn_batch;  // connects whose nearest node's row / whose candidate batch came from the record
   unsigned long long sc_wait;      // device-clock ticks the leader waited for the scout
   unsigned long long prof[32];     // device-clock ticks per planner phase (SMP_PROF_* in smp_kernels.hip)
   unsigned long long t0, t_first, t_end, deadline;  // device wall clock (0 deadline = none)
@@ -221,6 +222,8 @@ struct ScoutPre {
 // reports that the tree connect searches (tree_B of the iteration = tree_A of the one before) is final (its rewire
 // commits are done; nothing appends to it before connect): the nearest node of x_new, its near set (excluding the
 // id x_new has in its own tree, as find_near_vertices does) and the segment-norm sums of connect's edges.
+constexpr int CONN_ROWS = 20;  // near candidates of connect whose rows a record carries (near_set<20>: n_lo <= 20)
+static_assert(CONN_ROWS % 2 == 0 && CONN_ROWS <= MAXE, "ScoutConn: 8-byte words; the rows fill an edge batch");
 struct ScoutConn {
   double q[NJ];                // x_new
   double d;                    // distance of the nearest node (10000 if none)
@@ -235,6 +238,13 @@ struct ScoutConn {
   // checked to the end (a pure function of the two configurations): connect takes them instead of its two jobs
   int first0, nfirst;          // nfirst: candidates checked (-1: none, the record carries no validity)
   int first[MAX_NEAR];
+  // the tree rows the scout read to form the sums above, over the same final tree_B, so that the leader's connect
+  // loads none of them: the nearest node's (configuration, costs, parent) and those of the near candidates
+  // lo_i[e], e < nrow = min(n_lo, max_near) <= CONN_ROWS (-1: the record carries no rows)
+  double xq[NJ], xcost[3];
+  int xparent, nrow;
+  double rq[CONN_ROWS][NJ], rcost[CONN_ROWS][3];
+  int rparent[CONN_ROWS];
 };
 // Pre-solution record (DESIGN.md "Pre-solution commits"): everything pre_commit needs, written by the scout at the
 // end of its pass as data-tagged granules (tag = iteration + 1 in the high 32 bits, one 32-bit half of the struct

@@ -42,6 +42,7 @@ it = ((a >> np.uint64(54)) & np.uint64(0xff)).astype(int)
 line = ((a >> np.uint64(40)) & np.uint64(0x3fff)).astype(int)
 clk = (a & np.uint64(0xffffffffff)).astype(np.int64)
 TICK_US = 0.01  # wall clock 100 MHz
+TR_BAR0 = 16000  # smp_kernels.hip TR_BARRIERS: line field = TR_BAR0 + barriers of the leader's iteration
 src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "squirrel_motion_planner_amd",
                         "csrc", "smp_kernels.hip")).read().split("\n")
 
@@ -59,6 +60,13 @@ for rl in sorted(set(role.tolist())):
     m = role == rl
     order = np.argsort(clk[m], kind="stable")
     R_it, R_ln, R_ck = it[m][order], line[m][order], clk[m][order]
+    bar = R_ln >= TR_BAR0  # the leader's barrier counts (one record at each iteration's end), not trace points
+    if bar.any():
+        cnt = collections.Counter((R_ln[bar] - TR_BAR0).tolist())
+        print("\n=== role %d: __syncthreads() per iteration: median %d, min %d, max %d; count x iterations: %s" % (
+            rl, int(np.median(R_ln[bar] - TR_BAR0)), int(R_ln[bar].min() - TR_BAR0), int(R_ln[bar].max() - TR_BAR0),
+            " ".join("%dx%d" % kv for kv in sorted(cnt.items()))))
+        R_it, R_ln, R_ck = R_it[~bar], R_ln[~bar], R_ck[~bar]
     trans = collections.OrderedDict()
     its = sorted(set(R_it.tolist()))
     for k in range(len(R_ck) - 1):
@@ -71,7 +79,7 @@ for rl in sorted(set(role.tolist())):
     print("\n=== role %d (%s): %d iterations in window, %.1f us per iteration" % (
         rl, "leader" if rl == 0 else "scout %d" % rl, len(its), tot / max(len(its) - 1, 1)))
     rows = sorted(trans.items(), key=lambda kv: -kv[1][0])
-    for (l0, l1), (s, c) in rows[:40]:
+    for (l0, l1), (s, c) in rows[:int(os.environ.get("SMP_TRACE_ROWS", "40"))]:
         print("  %5.2f us/iter  %6.2f us x %4d   %4d %-22s -> %4d %-22s" % (
             s / max(len(its), 1), s / c, c, l0, func_of(l0)[:22], l1, func_of(l1)[:22]))
 
@@ -83,5 +91,8 @@ order = np.argsort(clk[sel], kind="stable")
 t0 = clk[sel][order][0] if sel.any() else 0
 print("\n=== timeline (iterations %d-%d of the window), us from the first record" % (w0, w0 + 1))
 for rl_, it_, ln_, ck_ in zip(role[sel][order], it[sel][order], line[sel][order], clk[sel][order]):
+    if ln_ >= TR_BAR0:
+        print("  %8.2f  L  it+%d  %d barriers in the iteration" % ((ck_ - t0) * TICK_US, it_ - w0, ln_ - TR_BAR0))
+        continue
     print("  %8.2f  %s it+%d  %4d %s" % ((ck_ - t0) * TICK_US, "L " if rl_ == 0 else "S%d" % rl_, it_ - w0, ln_,
                                          func_of(ln_)))
