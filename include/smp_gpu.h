@@ -174,6 +174,8 @@ typedef struct smp_stats {
                                     counts from run_planner entry, birrt_star.cpp:1075-1081); -1 if none */
   int64_t scout_conn_row_hits;   /* connects whose nearest node's row came from the scout's connect record */
   int64_t scout_conn_batch_hits; /* connects whose near candidates' rows came from the scout's connect record */
+  int64_t scout_conn_ov_hits;    /* scout passes whose connect scan of tree_B ran under the rewire job
+                                    (SMP_SCOUT_CONN_OV_MAX) */
 } smp_stats;
 
 typedef struct smp_result {

@@ -61,7 +61,7 @@ class Stats(ctypes.Structure):
                 ("scout_near_hits", _i64), ("scout_edge_hits", _i64), ("scout_edge_misses", _i64),
                 ("scout_wait_seconds", _d), ("scout_phase_seconds", _d * 32), ("helpers", ctypes.c_int32),
                 ("scout", ctypes.c_int32), ("time_first_solution_host", _d), ("scout_conn_row_hits", _i64),
-                ("scout_conn_batch_hits", _i64)]
+                ("scout_conn_batch_hits", _i64), ("scout_conn_ov_hits", _i64)]
 
 
 class Result(ctypes.Structure):

@@ -183,6 +183,7 @@ static QueryDev make_qdev(QueryBuffers& b, size_t cap, long long rows, const Pla
   d.scan_ps0 = k.scan_ps0;
   d.scan_pnn = k.scan_pnn;
   d.scan_pnear = k.scan_pnear;
+  d.conn_ov_max = k.scout_conn_ov_max;
   return d;
 }
 
@@ -199,6 +200,7 @@ struct PlanCall {
   std::vector<int> act;           // the queries still running
   std::vector<double> host_ttff;  // seconds from entry to each query's first path on the host's clock, -1: none yet
   std::vector<std::array<unsigned long long, 32>> scout_prof;
+  std::vector<unsigned long long> scout_conn_ov;  // the scouts' ScoutBoard::conn_ov_n, summed
   Provision prov;                 // the current launch's provisioning
   int nh_first = 0, ns_first = 0;  // the first provisioning's helpers and scouts (the statistics report them)
   float total_ms = 0;
@@ -405,6 +407,7 @@ static int plan_launch_loop(PlanCall& c) {
   int chunk = k.chunk0;
   c.scout_prof.resize(nq);
   for (auto& a : c.scout_prof) a.fill(0);
+  c.scout_conn_ov.assign(nq, 0);
   long long max_iters = 0;
   for (int i = 0; i < nq; ++i)
     if (qs[i].budget_kind != SMP_BUDGET_SECONDS) max_iters = std::max(max_iters, (long long)qs[i].budget);
@@ -480,9 +483,26 @@ static int plan_launch_loop(PlanCall& c) {
       HIPCHK(hipStreamSynchronize(p->stream));
       for (int i : act)
         for (int sc = 0; sc < ns; ++sc) {
-          unsigned long long sp[32];
-          HIPCHK(hipMemcpy(sp, c.qdev[i].scbs[sc]->prof, sizeof(sp), hipMemcpyDeviceToHost));
+          // conn_ov_n, cprof and prof lie side by side on the board: one copy
+          static_assert(offsetof(ScoutBoard, prof) - offsetof(ScoutBoard, conn_ov_n) == 7 * sizeof(unsigned long long),
+                        "ScoutBoard: conn_ov_n, cprof[6], prof[32]");
+          unsigned long long w[7 + 32];
+          HIPCHK(hipMemcpy(w, &c.qdev[i].scbs[sc]->conn_ov_n, sizeof(w), hipMemcpyDeviceToHost));
+          const unsigned long long* sp = w + 7;
           for (int j = 0; j < 32; ++j) c.scout_prof[i][j] += sp[j];
+          c.scout_conn_ov[i] += w[0];
+          if (i == 0 && k.conn_prof) {  // SMP_CONN_PROF builds (tools/perf_probe.py): PlanLds::cprof, two per word
+            unsigned v[12];
+            for (int j = 0; j < 12; ++j) v[j] = (unsigned)(w[1 + j / 2] >> (32 * (j & 1)));
+            const double us = p->wall_rate_hz * 1e-6;
+            auto per = [&](unsigned t, unsigned n) { return n ? t / us / n : 0.0; };
+            std::fprintf(stderr, "[smp] launch %lld scout %d: rewire jobs before a connect record %u, cgo there when the "
+                         "window opened %u; second near sets %u, %.2f us each; SC_DONE -> SC_CONN %u times, %.2f us each "
+                         "(cgo wait %.2f, scan %.2f, rest %.2f); rewire check %u times %.2f us, expand check %u times "
+                         "%.2f us\n", (long long)c.launches, sc, v[0], v[1], v[2], per(v[3], v[2]), v[4], per(v[5], v[4]),
+                         per(v[6], v[4]), per(v[7], v[4]), per(v[5] - v[6] - v[7], v[4]), v[9], per(v[8], v[9]), v[11],
+                         per(v[10], v[11]));
+          }
           if (i == 0 && k.debug_scouts) {  // per-scout passes and XCD (experiments)
             int xcc = 0;
             HIPCHK(hipMemcpy(&xcc, &c.qdev[i].scbs[sc]->xcc, sizeof(int), hipMemcpyDeviceToHost));
@@ -580,6 +600,7 @@ static int plan_assemble(PlanCall& c, smp_result* out, std::vector<char>& done) 
     st.scout_edge_misses = s.sc_edge_miss;
     st.scout_conn_row_hits = s.sc_conn_row;
     st.scout_conn_batch_hits = s.sc_conn_batch;
+    st.scout_conn_ov_hits = (int64_t)c.scout_conn_ov[i];
     st.scout_wait_seconds = (double)s.sc_wait / p->wall_rate_hz;
     for (int k = 0; k < 32; ++k) {
       const bool count = k == 8 || k == 11 || (k >= 20 && k < 28) || k == 30;

@@ -456,6 +456,20 @@ struct PlanLds {
   int n_at0;                    // leader: nodes of tree_A at the start of the iteration (early asks' snapshot)
   int sc_t, sc_rerun;           // scout: the pass's tree; 1 = the tree was rewired under the pass (rebuild it)
   int sc_stale_f;               // scout: the leader has passed the pass's iteration, as last read under a job (sc_early_send)
+  // scout, the rewire job's window (conn_window): ov_local = the scan under way stays on this workgroup
+  // (scan_split); conn_ov = connect's tree_B scan of this pass ran under the rewire job; conn_ov_n = such passes of
+  // this launch
+  int ov_local, conn_ov;
+  unsigned conn_ov_n;
+#ifdef SMP_CONN_PROF
+  // SMP_CONN_PROF builds (tools/perf_probe.py with SMP_CONN_PROF=1), scout, post-solution passes of this launch, counts
+  // and thread-0 clock ticks (32 bits each: runs of a few seconds): [0] rewire jobs of passes with a connect record to
+  // follow, [1] those that found cgo there when the window opened; [2] second near sets (x_new = the sample) and [3]
+  // their ticks; [4] scout_connect calls that sent a record, [5] their ticks in all, [6] waiting for cgo, [7] in the
+  // scan; [8] / [9] ticks and count of the rewire stage's edge_validity (job publication to the last collected tile,
+  // the window's work included), [10] / [11] the same of the expand stage's
+  unsigned cprof[12];
+#endif
   // scout: the rows of the near set's hi list (rewire's candidates: configuration, cost[0], parent), by position in
   // hi_i, loaded in the round trip of choose's candidate rows (near_set<20>: at most 20 entries)
   double sc_hq[MAXE][NJ], sc_hc[MAXE];
@@ -711,7 +725,7 @@ __device__ __forceinline__ int scan_parts(const Ctx& C, int near, int nodes) {
   return uni(P);
 }
 __device__ __forceinline__ bool scan_split(const Ctx& C, int nodes) {
-  return uni(C.Q.jb != nullptr && C.Q.scan_min > 0 && nodes >= C.Q.scan_min && C.Q.nworkers >= 8);
+  return uni(C.Q.jb != nullptr && C.Q.scan_min > 0 && nodes >= C.Q.scan_min && C.Q.nworkers >= 8 && !g_L.ov_local);
 }
 __device__ int nearest_dist(const Ctx& C, int t, const double* q, int i0, int n, double* d_out);
 __device__ void near_set_dist(const Ctx& C, int t, const double* q, int excl, bool nn);
@@ -2468,6 +2482,8 @@ __device__ __noinline__ unsigned job_tile_mask_out(const Ctx& C, JobLds& J, int 
 // Work the leader does while a collision job's tiles are checked by the helpers (see edge_validity).
 enum { OV_NONE = 0, OV_NEAR_EXPAND = 1, OV_NN = 2, OV_NEAR_XN = 3 };
 __device__ void overlap_work(const Ctx& C, int ov, int t);
+// Scout: connect's scan of tree t under the rewire job, in overlap_work's place (`conn_b` of edge_validity).
+__device__ void conn_window(const Ctx& C, int t);
 // Takes the result of overlap_work `ov` if that is what the last job computed: counts its scanned nodes.
 __device__ __forceinline__ bool take_spec(int ov) {
   const bool hit = uni(g_L.spec) == ov;
@@ -2571,7 +2587,7 @@ __device__ __forceinline__ void job_header(const Ctx& C, bool need, bool sfv) {
 // no claim is needed).
 // edge_validity has run job_header and set eg_first of the batch's edges to "free", and a barrier followed.
 __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot, int ov, int ovt, int early = 0,
-                                                  int epar = 0) {
+                                                  int epar = 0, bool conn_b = false) {
   JobBoard* jb = C.Q.jb;
   auto& J = g_L.u.job;
   const int np1 = g_L.S.n_pts + 1;
@@ -2610,7 +2626,8 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
   if (threadIdx.x == 0) g_L.in_job = 1;  // the helpers are on this job's tiles: overlap scans stay local
   sc_early_send(C, early, epar, E, false);
   __syncthreads();
-  overlap_work(C, ov, ovt);
+  if (conn_b) conn_window(C, ovt);
+  else overlap_work(C, ov, ovt);
   if (threadIdx.x == 0) g_L.in_job = 0;
   TR();
   // the leader's own tiles (in skip mode published too: the helpers' skip decisions read every earlier tile)
@@ -3650,8 +3667,15 @@ __device__ __noinline__ void local_tile(const Ctx& C, int nc) {
 // function of the two configurations) and is left out of the job.
 // `early` / `epar` (scout, post-solution pass): the record stage whose early words go out under the job
 // (sc_early_send), and the record slot; on every path they are stored, and g_L.sc_stale_f set, before the return.
+// `conn_b` (scout, the rewire stage's check; a constant at every call): under the job, conn_window(C, ovt) runs in
+// overlap_work's place.  It is a constant flag and a function of its own, not one more OV_* code, on purpose: as a code
+// of overlap_work the window's branch and its near_set<20, true> call were compiled into every inlined copy of
+// overlap_work whose `ov` is not a literal (the leader's connect_graphs grew by 1.6 KB, SGPR spills 377 -> 393), and
+// overlap_work's growth is what the inliner once answered by outlining it (tools/experiments/README.md, the fused
+// tree_B scans).  With
+// the flag false, which it is at every call but one, edge_validity compiles to the parent's code.
 __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_first_valid, int pslot, int ov = 0, int ovt = 0,
-                              int sgrp = -1, int early = 0, int epar = 0) {
+                              int sgrp = -1, int early = 0, int epar = 0, bool conn_b = false) {
   const int np1 = g_L.S.n_pts + 1;
   if (threadIdx.x == 0) g_L.count_slot = pslot + 4;
   TR();
@@ -3700,7 +3724,7 @@ __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_fir
       TR();
       return;
     }
-    edge_validity_job(C, E, pslot, ov, ovt, early, epar);
+    edge_validity_job(C, E, pslot, ov, ovt, early, epar, conn_b);
     if (sgrp >= 0) {  // (without a record stage no edge has a record result: eg_hit is -2 throughout)
       if (threadIdx.x < E && g_L.eg_hit[threadIdx.x] >= 0) g_L.eg_first[threadIdx.x] = g_L.eg_hit[threadIdx.x];
       __syncthreads();
@@ -3754,6 +3778,7 @@ __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_fir
     }
   }
   __syncthreads();
+  // (no job, no window: conn_b is not looked at here, the scan follows SC_DONE in scout_connect as before)
   overlap_work(C, ov, ovt);
 }
 
@@ -3785,6 +3810,37 @@ __device__ void overlap_work(const Ctx& C, int ov, int t) {
     g_L.spec = ov;
   }
   __syncthreads();
+}
+
+// Scout, post-solution pass, while its rewire job's tiles are checked (edge_validity's window): connect's scan of tree
+// t = tree_B for x_new, if a connect record follows (two scouts), the leader has reported that tree final and it holds at
+// most QueryDev::conn_ov_max nodes.  scout_connect then goes straight to the rows (g_L.conn_ov).
+__device__ void conn_window(const Ctx& C, int t) {
+  t = uni(t);
+  // one look at cgo, no wait: tree_B of the pass's iteration final -> its size, the acquire and the scan of
+  // scout_connect; else nothing (scout_connect then polls and scans as without the window).  The scan writes lo_*, hi_*,
+  // nk, n_lo, n_hi, fnn_* and S.n[t]: the rewire stage read its candidates from them before the job (scout_iteration)
+  if (threadIdx.x == 0) {
+    const bool on = g_L.two_scouts && C.Q.conn_ov_max > 0;
+#ifdef SMP_CONN_PROF
+    g_L.cprof[0] += g_L.two_scouts != 0;
+    g_L.cprof[1] += g_L.two_scouts && (unsigned)(ld_agent(&C.Q.scb->cgo) >> 32) == (unsigned)(g_L.sc_k + 1);
+#endif
+    const unsigned long long v = on ? ld_agent(&C.Q.scb->cgo) : 0ull;
+    const int nb = (int)(unsigned)v;
+    const int go = on && (unsigned)(v >> 32) == (unsigned)(g_L.sc_k + 1) && nb <= C.Q.conn_ov_max;
+    if (go) { g_L.S.n[t] = nb; g_L.ov_local = 1; g_L.conn_ov_n++; }
+    g_L.conn_ov = go;
+    g_L.spec = OV_NONE;
+  }
+  __syncthreads();
+  if (uni(g_L.conn_ov)) {
+    // the tree's stores are the leader's (drained before cgo): drop stale cached copies
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    near_set<20, true>(C, t, g_L.xn.q, g_L.xn.id);
+    if (threadIdx.x == 0) g_L.ov_local = 0;
+    __syncthreads();
+  }
 }
 
 // Reference-semantics accounting of one isEdgeValid call (stops at the first collision).
@@ -5660,7 +5716,12 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
   ScoutRec& R = g_L.sr;
   ScoutBoard* sb = C.Q.scb;
   const int tb = 1 - t;
-  for (int k = 0;; k ^= 1) {
+  // (the rewire job's window has seen cgo and run the scan, conn_window: straight to the rows)
+  const bool scanned = uni(g_L.conn_ov) != 0;
+#ifdef SMP_CONN_PROF
+  const unsigned long long _c0 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
+  for (int k = 0; !scanned; k ^= 1) {
     if (threadIdx.x == 0) {
       const unsigned long long v = ld_agent(&sb->cgo);
       int go = 0;
@@ -5677,12 +5738,20 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
     if (go > 0) break;
     __builtin_amdgcn_s_sleep(2);
   }
-  // the tree's stores are the leader's (drained before cgo): drop stale cached copies
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  if (threadIdx.x == 0) g_L.S.n[tb] = g_L.cnt;
-  __syncthreads();
-  // the near set of x_new and its nearest node (no exclusion) in one pass over tree_B
-  [[clang::always_inline]] near_set<20, true>(C, tb, g_L.xn.q, g_L.xn.id);
+#ifdef SMP_CONN_PROF
+  const unsigned long long _c1 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
+  if (!scanned) {
+    // the tree's stores are the leader's (drained before cgo): drop stale cached copies
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (threadIdx.x == 0) g_L.S.n[tb] = g_L.cnt;
+    __syncthreads();
+    // the near set of x_new and its nearest node (no exclusion) in one pass over tree_B
+    [[clang::always_inline]] near_set<20, true>(C, tb, g_L.xn.q, g_L.xn.id);
+  }
+#ifdef SMP_CONN_PROF
+  const unsigned long long _c2 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
   if (threadIdx.x == 0) {
     double d = g_L.fnn_d;
     int cid = g_L.fnn_id;
@@ -5747,6 +5816,12 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
   __syncthreads();
   sc_copy_out(sb, par, &R.cc, sizeof(ScoutConn));
   sc_publish(C, par, tag, SC_CONN);
+#ifdef SMP_CONN_PROF
+  if (threadIdx.x == 0) {
+    g_L.cprof[4]++;
+    g_L.cprof[5] += (unsigned)(wall_clock64() - _c0); g_L.cprof[6] += (unsigned)(_c1 - _c0); g_L.cprof[7] += (unsigned)(_c2 - _c1);
+  }
+#endif
 }
 
 // Scout: ends a record without connect's scans; a post-solution record of two scouts still reaches stage SC_CONN
@@ -5933,6 +6008,7 @@ __device__ void scout_iteration(const Ctx& C, long long it, int t, int X, int op
     R.cn.ok = 0;
     R.pre.ok = 0;
     R.nn.ok = 0; R.ex.ok = 0; R.nr.ok = 0; R.n_choose = 0; R.n_rewire = 0; R.cc.ok = 0; R.cc.nfirst = -1;
+    g_L.conn_ov = 0;
   }
   // the sample: the sampler's ring slot for (it, ver), if it is there within ~20 us.  The first round's loads are
   // issued before SC_STARTED's drain, which then waits for them too: one round trip instead of two at the pass's start
@@ -6051,8 +6127,14 @@ redo:
     [[clang::always_inline]] edge_validity(C, 2, false, P_XEXPAND, OV_NONE, t);
   } else {
     // (post-solution: R.ex and the edge's start, target and sums go out under the job, sc_early_send)
+#ifdef SMP_CONN_PROF
+    const unsigned long long _e0 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
     [[clang::always_inline]] edge_validity(C, 1, false, P_XEXPAND, opt ? OV_NEAR_EXPAND : OV_NONE, t, -1,
                                            opt ? EARLY_EXPAND : EARLY_NONE, par);
+#ifdef SMP_CONN_PROF
+    if (threadIdx.x == 0 && opt) { g_L.cprof[10] += (unsigned)(wall_clock64() - _e0); g_L.cprof[11]++; }
+#endif
   }
   if (opt) sc_first_send(C, EARLY_EXPAND, par, 1);
   if (threadIdx.x == 0) {
@@ -6139,7 +6221,13 @@ redo:
   if (sc_moved(C)) return;
   // near set of x_new (the leader's, before choose_parent)
   if (!(uni(g_L.ext_nn) && take_spec(OV_NEAR_EXPAND))) {
+#ifdef SMP_CONN_PROF
+    const unsigned long long _n0 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
     [[clang::always_inline]] near_set<20>(C, t, g_L.xn.q, X);
+#ifdef SMP_CONN_PROF
+    if (threadIdx.x == 0) { g_L.cprof[2]++; g_L.cprof[3] += (unsigned)(wall_clock64() - _n0); }
+#endif
   }
   if (threadIdx.x < 20) {
     R.nr.lo_i[threadIdx.x] = g_L.lo_i[threadIdx.x]; R.nr.lo_c[threadIdx.x] = g_L.lo_c[threadIdx.x];
@@ -6267,7 +6355,16 @@ redo:
     for (int e = cnt + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
     if (threadIdx.x == 0) R.n_rewire = cnt;  // (sent with the candidates' early words, under the job)
     __syncthreads();
-    [[clang::always_inline]] edge_validity(C, cnt, false, P_XREWIRE, OV_NONE, 0, -1, EARLY_REWIRE, par);
+    // connect's scan of tree_B under the job (conn_window) when the leader has reported the tree final by
+    // then.  It writes nk, n_lo, n_hi, lo_*, hi_*, fnn_* and S.n[1 - t]: this stage read hi_i, nk, n_hi and sc_h* above,
+    // before the job; after it only eg_need / eg_first are read (sc_first_send), and scout_connect reads the scan
+#ifdef SMP_CONN_PROF
+    const unsigned long long _r0 = threadIdx.x == 0 ? wall_clock64() : 0;
+#endif
+    [[clang::always_inline]] edge_validity(C, cnt, false, P_XREWIRE, OV_NONE, 1 - t, -1, EARLY_REWIRE, par, true);
+#ifdef SMP_CONN_PROF
+    if (threadIdx.x == 0) { g_L.cprof[8] += (unsigned)(wall_clock64() - _r0); g_L.cprof[9]++; }
+#endif
     sc_first_send(C, EARLY_REWIRE, par, cnt);
   } else {
     sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
@@ -6313,6 +6410,10 @@ __device__ __noinline__ void scout_main(Ctx& C, int which) {
     g_L.count_slot = 0;
     g_L.job_seq = 0;
     g_L.in_job = 0;
+    g_L.ov_local = 0; g_L.conn_ov = 0; g_L.conn_ov_n = 0;
+#ifdef SMP_CONN_PROF
+    for (int k = 0; k < 12; ++k) g_L.cprof[k] = 0;
+#endif
     g_L.n_via = 0;
     g_L.near_blo = ~0ull;
     g_L.near_bhi = 0;
@@ -6458,6 +6559,10 @@ __device__ __noinline__ void scout_main(Ctx& C, int which) {
   if (threadIdx.x == 0) {
     st_agent(&C.Q.jb->stop, 1);
     for (int k = 0; k < 32; ++k) st_agent(&C.Q.scb->prof[k], g_L.S.prof[k]);
+    st_agent(&C.Q.scb->conn_ov_n, (unsigned long long)g_L.conn_ov_n);
+#ifdef SMP_CONN_PROF
+    for (int k = 0; k < 6; ++k) st_agent(&C.Q.scb->cprof[k], (unsigned long long)g_L.cprof[2 * k] | (unsigned long long)g_L.cprof[2 * k + 1] << 32);
+#endif
   }
 }
 
@@ -6616,6 +6721,7 @@ __global__ void __launch_bounds__(BLOCK) plan_kernel(const RobotDev* __restrict_
     g_L.count_slot = 0;
     g_L.job_seq = 0;
     g_L.in_job = 0;
+    g_L.ov_local = 0;
     g_L.S = *C.Q.st;
     if (g_L.S.phase == 0 && g_L.S.t0 == 0) {
       g_L.S.t0 = wall_clock64();
@@ -6802,6 +6908,7 @@ __device__ __forceinline__ void near_probe_body(const double* tqv, const double*
   C.Q.tr[0].cost = const_cast<double*>(tcost);
   if (threadIdx.x == 0) {
     g_L.in_job = 0;
+    g_L.ov_local = 0;
     g_L.S.n[0] = n;
     g_L.S.cap = cap;
     g_L.S.near_r = r;

@@ -302,7 +302,9 @@ struct ScoutBoard {
   int pad2[28];
   unsigned long long stage[SCOUT_SLOTS];  // scout -> leader, by iteration mod SCOUT_SLOTS
   unsigned long long cgo;      // leader -> scout: granule (iteration k + 1, n of tree_B(k)) once tree_B(k) is final
-  int pad1[14];
+  // passes of the launch whose connect scan ran in the rewire job's window (written when the scout leaves)
+  unsigned long long conn_ov_n;
+  unsigned long long cprof[6]; // SMP_CONN_PROF builds: the scout's twelve connect counts and clocks of the launch, in pairs
   unsigned long long prof[32]; // the scout's phase clocks of the launch (written when it leaves)
   ScoutRec rec[SCOUT_SLOTS];
   ViaNode pre_via[SCOUT_SLOTS][PRE_VIA];  // ScoutPre's via chains, by record slot
@@ -358,6 +360,9 @@ struct QueryDev {
   double* rows;                // [max_iter][5] cost evolution rows (may be null)
   long long rows_cap;
   int* path_nodes;             // [2][cap] path extraction scratch
+  // scout, post-solution passes: a tree_B of up to this many nodes is scanned for connect under the rewire job, once the
+  // leader has reported it final (0: off, the scan follows the rewire record)
+  int conn_ov_max;
 };
 
 }  // namespace smp

@@ -85,6 +85,17 @@ PlanKnobs read_plan_knobs(int helpers, int nq) {
   // several queries start at 256 iterations and double, so that finished ones free their CUs early (rebalance)
   k.chunk0 = nq == 1 || k.slice_ms > 0 ? (1 << 30) : 256;
   if (const char* e = std::getenv("SMP_CHUNK0")) k.chunk0 = std::max(1, std::atoi(e));  // experiments
+  // post-solution scout passes (DESIGN.md §5 "Round 13"): a tree_B of up to this many nodes is scanned for connect
+  // under the pass's rewire job instead of after it (0: off).  The window's scan stays on the scout's workgroup at any
+  // size, and a local scan grows with the tree while the job's window does not.  Measured: at C2's 3-4 k nodes the
+  // scout's rewire stage 8.8 -> 9.7 us per pass and the iteration 49.2 -> 47.6 us; at 13.8 k nodes (20000 iterations)
+  // the iteration 58.1 us with the gate at 2048, 56.4 at 8192 and 54.1 without a gate.  So 8192 is not the optimum at
+  // those sizes: it is the largest size up to which the suite holds the window to the oracle (the 1e5- and 3e5-iteration
+  // runs pass through it); above it parity was only probed, not tested, and far above scan_min a local scan outlasts
+  // any job.
+  k.scout_conn_ov_max = 8192;
+  if (const char* e = std::getenv("SMP_SCOUT_CONN_OV_MAX")) k.scout_conn_ov_max = std::max(0, std::atoi(e));
+  k.conn_prof = std::getenv("SMP_CONN_PROF") != nullptr;  // SMP_CONN_PROF builds: the scouts' connect clocks per launch
   return k;
 }
 

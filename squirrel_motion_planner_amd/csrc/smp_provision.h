@@ -38,6 +38,8 @@ struct PlanKnobs {
   double wait_slack_s;  // SMP_WAIT_SLACK_S
   int chunk0;           // SMP_CHUNK0: iterations of the first launch
   bool host_prof, debug, debug_scouts, bounds;  // SMP_HOST_PROF, SMP_DEBUG, SMP_DEBUG_SCOUTS, SMP_BOUNDS: set at all
+  bool conn_prof;         // SMP_CONN_PROF: print the scouts' connect clocks per launch (SMP_CONN_PROF builds)
+  int scout_conn_ov_max;  // SMP_SCOUT_CONN_OV_MAX: nodes up to which a scout scans tree_B for connect under its rewire job
 };
 
 // helpers: smp_params.helpers; nq: queries of the call.

@@ -36,6 +36,8 @@ for iters in [int(v) for v in (sys.argv[1:] or ["2000", "10000", "50000"])]:
     print("   helpers %d scout %d: nn hits %d, near hits %d, edge hits %d misses %d, leader waited %.1f us/iter" % (
         r["helpers"], r["scout"], r["scout_nn_hits"], r["scout_near_hits"], r["scout_edge_hits"],
         r["scout_edge_misses"], r["scout_wait_seconds"] * 1e6 / max(r["iterations"], 1)), flush=True)
+    print("   scout: connect scan in the rewire job's window %d passes; connect rows from the record %d" % (
+        r["scout_conn_ov_hits"], r["scout_conn_row_hits"]), flush=True)
     sp = r["scout_phases"]
     if sp[30] > 0:
         ns = sp[30]
