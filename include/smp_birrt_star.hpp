@@ -271,6 +271,23 @@ class BiRRTstarPlanner {
     return first < 0;
   }
 
+  // Not in the reference: isEdgeValid with a safety margin (smp_check_edges_margin; include/smp_gpu.h "Margin checks"):
+  // true if every point of the edge is valid and farther than margin_map metres from the map and margin_self metres
+  // from self-collision.  last_clear_node_idx reads as isEdgeValid's index.
+  bool isEdgeClear(const vector<double>& from, const vector<double>& to, int& last_clear_node_idx,
+                   bool check_self_collision, bool check_map_collision, double margin_map, double margin_self) {
+    need();
+    last_clear_node_idx = 0;
+    if (from.size() != 8 || to.size() != 8) return false;
+    const smp_margin m = {margin_map, margin_self};
+    int64_t first = -1;
+    int32_t n_points = 0;
+    check(smp_check_edges_margin(planner_, from.data(), to.data(), 1, check_self_collision, check_map_collision, &m,
+                                 &first, &n_points), "isEdgeClear");
+    last_clear_node_idx = first < 0 ? n_points - 1 : (first > 0 ? (int)first - 1 : 0);
+    return first < 0;
+  }
+
   // Shortens a trajectory in place (smp_shortcut_path): every waypoint pair within `window` (0: all pairs) is checked
   // as a dense edge in one launch, the cheapest route through the free ones is kept and the via nodes of its edges are
   // inserted, so consecutive poses stay at most one planner step apart.  The node calls it between
@@ -278,6 +295,22 @@ class BiRRTstarPlanner {
   // fewer than two poses: there is no edge to check).
   bool shortcutTrajectory(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
                           int window = 0) {
+    return shortcutWith(trajectory, check_self_collision, check_map_collision, window, nullptr);
+  }
+  // The same with a safety margin (smp_shortcut_path_margin): the route runs through the pairs whose every point is
+  // farther than margin_map metres from the map and margin_self metres from self-collision.  After
+  // repairTrajectory with the same margins it leaves a trajectory that keeps that distance.
+  bool shortcutTrajectory(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
+                          int window, double margin_map, double margin_self) {
+    const smp_margin m = {margin_map, margin_self};
+    return shortcutWith(trajectory, check_self_collision, check_map_collision, window, &m);
+  }
+  // Counts, costs and timing of the last shortcutTrajectory.
+  const smp_shortcut_info& lastShortcut() const { return shortcut_; }
+
+ private:
+  bool shortcutWith(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
+                    int window, const smp_margin* margin) {
     need();
     if (trajectory.size() < 2) return false;
     vector<double> rows;
@@ -288,8 +321,11 @@ class BiRRTstarPlanner {
     }
     double* out = nullptr;
     int64_t n_out = 0;
-    const int st = smp_shortcut_path(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
-                                     check_map_collision, window, &out, &n_out, &shortcut_);
+    const int st =
+        margin ? smp_shortcut_path_margin(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
+                                          check_map_collision, window, margin, &out, &n_out, &shortcut_)
+               : smp_shortcut_path(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
+                                   check_map_collision, window, &out, &n_out, &shortcut_);
     if (st == SMP_ERR_NO_SOLUTION) return false;
     check(st, "shortcutTrajectory");
     vector<vector<double> > res((size_t)n_out, vector<double>(8));
@@ -299,9 +335,8 @@ class BiRRTstarPlanner {
     trajectory.swap(res);
     return true;
   }
-  // Counts, costs and timing of the last shortcutTrajectory.
-  const smp_shortcut_info& lastShortcut() const { return shortcut_; }
 
+ public:
   // Repairs a trajectory in place (smp_repair_path): the stretches that fail the dense check (the planner's own paths
   // can, and the scene may have changed since planning) are gathered into gaps between valid poses and each is bridged
   // by the cheapest free one-via detour of `samples` per round, the sampling half width doubling over `rounds`; the via
@@ -310,6 +345,21 @@ class BiRRTstarPlanner {
   // an end pose is invalid or there are fewer than two poses.
   bool repairTrajectory(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
                         int samples = 256, int rounds = 4, unsigned long long seed = 1) {
+    return repairWith(trajectory, check_self_collision, check_map_collision, samples, rounds, seed, nullptr);
+  }
+  // The same with a safety margin (smp_repair_path_margin): every stretch that is not clear at the margins is bridged
+  // by a detour that is; an end pose that is not clear gives false.
+  bool repairTrajectory(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision,
+                        int samples, int rounds, unsigned long long seed, double margin_map, double margin_self) {
+    const smp_margin m = {margin_map, margin_self};
+    return repairWith(trajectory, check_self_collision, check_map_collision, samples, rounds, seed, &m);
+  }
+  // Counts, costs and timing of the last repairTrajectory.
+  const smp_repair_info& lastRepair() const { return repair_; }
+
+ private:
+  bool repairWith(vector<vector<double> >& trajectory, bool check_self_collision, bool check_map_collision, int samples,
+                  int rounds, unsigned long long seed, const smp_margin* margin) {
     need();
     if (trajectory.size() < 2) return false;
     vector<double> rows;
@@ -325,8 +375,11 @@ class BiRRTstarPlanner {
     o.seed = seed;
     double* out = nullptr;
     int64_t n_out = 0;
-    const int st = smp_repair_path(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
-                                   check_map_collision, &o, &out, &n_out, &repair_);
+    const int st =
+        margin ? smp_repair_path_margin(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
+                                        check_map_collision, &o, margin, &out, &n_out, &repair_)
+               : smp_repair_path(planner_, rows.data(), (int64_t)trajectory.size(), check_self_collision,
+                                 check_map_collision, &o, &out, &n_out, &repair_);
     if (st == SMP_ERR_NO_SOLUTION || st == SMP_ERR_START_INVALID || st == SMP_ERR_GOAL_INVALID) return false;
     check(st, "repairTrajectory");
     vector<vector<double> > res((size_t)n_out, vector<double>(8));
@@ -336,8 +389,8 @@ class BiRRTstarPlanner {
     trajectory.swap(res);
     return true;
   }
-  // Counts, costs and timing of the last repairTrajectory.
-  const smp_repair_info& lastRepair() const { return repair_; }
+
+ public:
 
   // Clearance (not in the reference, whose getCollisions lists contacts only once they exist): how far a configuration
   // or a dense edge is from the map and from self-collision, and which links are nearest (include/smp_gpu.h "Clearance

@@ -465,6 +465,46 @@ int smp_clearance_configs(smp_planner* p, const double* q_rows, int64_t n, doubl
 int smp_clearance_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, double max_dist,
                         int with_self, int with_map, smp_edge_clearance* out, smp_clearance_info* info);
 
+/* Margin checks: the path passes with a safety margin.  The validity checks answer "does it touch?", the clearance
+ * queries "how far is it?"; these answer "is every point farther than the margin?", with the early exits of the former,
+ * and carry that predicate through the dense edge check, the shortcut and the repair.
+ *
+ * Definition.  A configuration q is clear at the margins (mm, ms) = (margin->map, margin->self) under the flags
+ * (check_self, check_map) iff all of
+ *   1. it is valid by smp_check_configs with the same flags;
+ *   2. if check_map and mm > 0: every map term of the "Clearance queries" definition above is > mm -- the same
+ *      expressions in the same order, the same disabled links, a centre outside the grid is free; equivalently
+ *      smp_clearance_configs(q, D).map > mm for any admissible D > mm;
+ *   3. if check_self and ms > 0: every self term of that definition is > ms, i.e. .self > ms.
+ * The comparison is made on the term as that definition rounds it, e.g. fl(fl(sqrt(s)) - r) > mm, and it is strict.  A
+ * part whose margin is 0 is the boolean test of that part, untouched.  By the monotonicity note above (sqrt is monotone
+ * and sqrt(fl(r * r)) == r) 2 and 3 imply 1 for a part whose margin is positive, so the kernel skips the boolean test of
+ * that part; the tests compare against the conjunction.
+ * An edge is clear iff all points 0..M of the density rule are; first_invalid is the lowest point that is not clear.
+ * SMP_ERR_ARG: a margin that is not finite or is negative; a map margin whose largest prefilter threshold
+ * floor(((r + mm + 1e-6) / res)^2) reaches the clamp of the box-gap field (the rule of smp_clearance_* for max_dist); a
+ * positive map margin with check_map and no scene.  A NULL margin or {0, 0} gives results identical to the plain entry
+ * point in every output field (a margin of a part not asked for counts as 0).
+ *
+ * Each entry point takes the plain call's arguments plus the margin; semantics, errors, capacities, info records and
+ * output rows are those of the plain call with "valid / free" read as "clear" (smp_repair_path_margin: an unclear first
+ * or last waypoint gives SMP_ERR_START_INVALID / SMP_ERR_GOAL_INVALID).  smp_check_configs_margin takes its
+ * configurations row-major (n x 8) and writes clear[i] = 1 iff configuration i is clear. */
+typedef struct smp_margin { double map, self; } smp_margin;   /* metres; NULL means {0, 0} */
+int smp_check_configs_margin(smp_planner* p, const double* q_rows, int64_t n, int check_self, int check_map,
+                             const smp_margin* margin, uint8_t* clear);
+int smp_check_edges_margin(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, int check_self,
+                           int check_map, const smp_margin* margin, int64_t* first_invalid, int32_t* n_points);
+int smp_sample_detours_margin(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps,
+                              int samples, double half_width, uint64_t seed, uint32_t round, int check_self,
+                              int check_map, const smp_margin* margin, smp_detour* out);
+int smp_shortcut_path_margin(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                             int window, const smp_margin* margin, double** out_waypoints, int64_t* n_out,
+                             smp_shortcut_info* info);
+int smp_repair_path_margin(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                           const smp_repair_opts* opts, const smp_margin* margin, double** out_waypoints,
+                           int64_t* n_out, smp_repair_info* info);
+
 /* n poses of `dim` values, row-major.  *n_out = rows of the normalized trajectory; with out == NULL only counts,
  * else writes them (SMP_ERR_CAPACITY if out_cap < *n_out).  For dim < 1 or n <= 1 the reference leaves its output
  * untouched: *n_out = 0.  Host only (no GPU needed). */

@@ -118,6 +118,11 @@ class RepairInfo(ctypes.Structure):
                 ("kernel_ms", _d), ("total_ms", _d)]
 
 
+class Margin(ctypes.Structure):
+    """smp_margin: the distances (metres) a margin check keeps from the map and from self-collision."""
+    _fields_ = [("map", _d), ("self", _d)]
+
+
 class Clearance(ctypes.Structure):
     """smp_clearance: map and self clearance of one configuration with the witness links."""
     _fields_ = [("map", _d), ("self", _d), ("map_link", ctypes.c_int32), ("self_a", ctypes.c_int32),
@@ -195,6 +200,15 @@ EXPORTS = [
                                    ctypes.POINTER(ClearanceInfo)]),
     ("smp_clearance_edges", _i, [_p, _pd, _pd, _i64, _d, _i, _i, ctypes.POINTER(EdgeClearance),
                                  ctypes.POINTER(ClearanceInfo)]),
+    ("smp_check_configs_margin", _i, [_p, _pd, _i64, _i, _i, ctypes.POINTER(Margin), _p]),
+    ("smp_check_edges_margin", _i, [_p, _pd, _pd, _i64, _i, _i, ctypes.POINTER(Margin), ctypes.POINTER(_i64),
+                                    ctypes.POINTER(ctypes.c_int32)]),
+    ("smp_sample_detours_margin", _i, [_p, _pd, _pd, _i64, _i, _d, ctypes.c_uint64, ctypes.c_uint32, _i, _i,
+                                       ctypes.POINTER(Margin), ctypes.POINTER(Detour)]),
+    ("smp_shortcut_path_margin", _i, [_p, _pd, _i64, _i, _i, _i, ctypes.POINTER(Margin), ctypes.POINTER(_pd),
+                                      ctypes.POINTER(_i64), ctypes.POINTER(ShortcutInfo)]),
+    ("smp_repair_path_margin", _i, [_p, _pd, _i64, _i, _i, ctypes.POINTER(RepairOpts), ctypes.POINTER(Margin),
+                                    ctypes.POINTER(_pd), ctypes.POINTER(_i64), ctypes.POINTER(RepairInfo)]),
     ("smp_normalize_trajectory", _i, [_pd, _i64, _i, _pd, _pd, _i64, ctypes.POINTER(_i64)]),
     ("smp_ik_solve", _i, [_p, ctypes.POINTER(IkRequest), _i, ctypes.POINTER(IkResult)]),
     ("smp_find_goal_pose", _i, [_p, _pd, _pd, _d, _i, _i, _pd, ctypes.POINTER(_i), ctypes.POINTER(GoalSearch)]),

@@ -1,7 +1,7 @@
 // C ABI implementation (include/smp_gpu.h), path tools: batched dense edge checks, shortcutting, one-via detours and
-// path repair, clearance queries (kernels: smp_edges.hip, smp_repair.hip, smp_clearance.hip).  Every entry point
-// validates, builds its tables, launches (run_pass), post-processes and fills its info record; the plain logic between
-// the launches is smp_paths.cpp's.
+// path repair, clearance queries and the margin variants of the passes (kernels: smp_edges.hip, smp_repair.hip,
+// smp_clearance.hip, smp_margin.hip).  Every entry point validates, builds its tables, launches (run_pass),
+// post-processes and fills its info record; the plain logic between the launches is smp_paths.cpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,11 +67,52 @@ static int upload_edges(smp_planner* p, const std::vector<EdgeDev>& edges, const
   return upload(p, p->d_eorder, order.data(), order.size());
 }
 
-extern "C" {
+// ------------------------------------------------------------------------------------------ the passes' predicate
+// How a call checks its configurations, edges and detour items: the flags, and the margin tables when a part asked for
+// has a positive margin (mg != nullptr: the kernels of smp_margin.hip; else the plain ones).  The host logic between
+// the launches consumes valid, first_invalid and free and does not care which predicate produced them.
+struct Checks {
+  int self, map;
+  const MarginCfg* mg;
+};
 
-// ------------------------------------------------------------------------------------------ dense edge checks
-// One edges_kernel launch over the table: first[i] = first colliding point of edge i, -1 if it is free.
-static int run_edges(smp_planner* p, const std::vector<EdgeDev>& edges, int self, int map, std::vector<int>& first,
+// The margin tables of one call into *c; *on = whether a part asked for has a positive margin (false: the call is the
+// plain one).  SMP_ERR_ARG for a margin that is not finite or negative, or a map margin whose largest prefilter
+// threshold reaches the box-gap field's clamp (clear_cfg's rule for max_dist).
+static int margin_cfg(const smp_planner* p, const smp_margin* margin, int self, int map, MarginCfg* c, bool* on) {
+  *on = false;
+  const double mm = margin ? margin->map : 0.0, ms = margin ? margin->self : 0.0;
+  if (!std::isfinite(mm) || !std::isfinite(ms) || mm < 0.0 || ms < 0.0) return SMP_ERR_ARG;
+  std::memset(c, 0, sizeof(*c));
+  c->self = self ? 1 : 0;
+  c->map = (map && p->have_scene) ? 1 : 0;
+  c->mm = map ? mm : 0.0;
+  c->ms = self ? ms : 0.0;
+  if (c->mm > 0.0) {
+    const RobotDev& d = p->robot.dev;
+    auto threshold = [&](double r, uint32_t* out) {
+      const double a = (r + c->mm + 1e-6) / p->scene_res;
+      const double t = std::floor(a * a);
+      if (!(t < 65535.0)) return false;
+      *out = (uint32_t)t;
+      return true;
+    };
+    for (int s = 0; s < d.n_sph; ++s) {
+      if (!threshold(d.sph_r[s], &c->T[s])) return SMP_ERR_ARG;
+      c->S[s] = margin_threshold(d.sph_r[s], c->mm);
+    }
+    for (int k = 0; k < d.n_prim; ++k) {
+      const double hz = d.prim_type[k] == 1 ? d.prim_h[k * 3 + 2] : d.prim_h[k * 3 + 1];
+      if (!threshold(std::sqrt(d.prim_rxy[k] * d.prim_rxy[k] + hz * hz), &c->pT[k])) return SMP_ERR_ARG;
+    }
+    c->Sp = margin_threshold(0.0, c->mm);
+  }
+  *on = c->mm > 0.0 || c->ms > 0.0;
+  return SMP_OK;
+}
+
+// One launch over the table: first[i] = the first point of edge i that fails the predicate, -1 if none does.
+static int run_edges(smp_planner* p, const std::vector<EdgeDev>& edges, const Checks& ck, std::vector<int>& first,
                      double* kernel_ms) {
   const size_t n = edges.size();
   const std::vector<int> order = longest_first(edges);
@@ -79,19 +120,51 @@ static int run_edges(smp_planner* p, const std::vector<EdgeDev>& edges, int self
   return run_pass(
       p, n, [&] { return upload_edges(p, edges, order); },
       [&](int grid) {
-        launch_edges(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_edges.p, p->d_eorder.p, (int)n, self,
-                     map && p->have_scene, p->d_ecounter.p, p->d_efirst.p);
+        if (ck.mg)
+          launch_margin_edges(grid, p->stream, p->d_rb, p->sc, p->d_mc, *ck.mg, p->d_edges.p, p->d_eorder.p, (int)n,
+                              p->d_ecounter.p, p->d_efirst.p);
+        else
+          launch_edges(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_edges.p, p->d_eorder.p, (int)n, ck.self,
+                       ck.map && p->have_scene, p->d_ecounter.p, p->d_efirst.p);
       },
       p->d_efirst, first.data(), n, kernel_ms);
 }
 
-// Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule.
-int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, int check_self,
-                    int check_map, int64_t* first_invalid, int32_t* n_points) {
-  if (!p || n < 0 || (n > 0 && (!from_rows || !to_rows || !first_invalid))) return SMP_ERR_ARG;
-  if (int b_ = busy_check(p)) return b_;
-  if (n == 0) return SMP_OK;
-  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+// One margin_configs_kernel launch: clear[i] for the n rows (row-major n x 8).
+static int run_margin_configs(smp_planner* p, const MarginCfg& mg, const double* q_rows, int64_t n, uint8_t* clear,
+                              double* kernel_ms) {
+  const int n_items = (int)((n + PASS_CT - 1) / PASS_CT);
+  return run_pass(
+      p, (size_t)n_items, [&] { return upload(p, p->d_clq, q_rows, (size_t)n * NJ); },
+      [&](int grid) {
+        launch_margin_configs(grid, p->stream, p->d_rb, p->sc, p->d_mc, mg, p->d_clq.p, (long long)n, n_items,
+                              p->d_ecounter.p, p->d_mclear.p);
+      },
+      p->d_mclear, clear, (size_t)n, kernel_ms);
+}
+
+static bool finite_rows(const double* rows, int64_t n) {
+  for (int64_t i = 0; i < n * NJ; ++i)
+    if (!std::isfinite(rows[i])) return false;
+  return true;
+}
+
+extern "C" {
+
+// The predicate on n rows (row-major n x 8): the batch checker, or the margin tiles.
+static int check_rows(smp_planner* p, const Checks& ck, const double* rows, int64_t n, uint8_t* ok, double* kernel_ms) {
+  if (ck.mg) return run_margin_configs(p, *ck.mg, rows, n, ok, kernel_ms);
+  std::vector<double> soa((size_t)n * NJ);
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < NJ; ++j) soa[(size_t)j * n + i] = rows[i * NJ + j];
+  const int st = smp_check_configs(p, soa.data(), n, ck.self, ck.map, ok);
+  if (st == SMP_OK) *kernel_ms = p->last_check_ms;
+  return st;
+}
+
+// ------------------------------------------------------------------------------------------ dense edge checks
+static int check_edges_body(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n,
+                            const Checks& ck, int64_t* first_invalid, int32_t* n_points) {
   if (n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   const EdgeRule rule = edge_rule(p);
   std::vector<EdgeDev> edges((size_t)n);
@@ -99,7 +172,7 @@ int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_ro
     if (!make_edge(rule, from_rows + i * NJ, to_rows + i * NJ, &edges[(size_t)i])) return SMP_ERR_ARG;
   std::vector<int> first;
   double ms = 0;
-  const int st = run_edges(p, edges, check_self, check_map, first, &ms);
+  const int st = run_edges(p, edges, ck, first, &ms);
   if (st != SMP_OK) return st;
   p->last_check_ms = ms;
   for (int64_t i = 0; i < n; ++i) {
@@ -109,10 +182,51 @@ int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_ro
   return SMP_OK;
 }
 
+// Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule.
+int smp_check_edges(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, int check_self,
+                    int check_map, int64_t* first_invalid, int32_t* n_points) {
+  if (!p || n < 0 || (n > 0 && (!from_rows || !to_rows || !first_invalid))) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  if (n == 0) return SMP_OK;
+  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+  return check_edges_body(p, from_rows, to_rows, n, Checks{check_self, check_map, nullptr}, first_invalid, n_points);
+}
+
+int smp_check_edges_margin(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n, int check_self,
+                           int check_map, const smp_margin* margin, int64_t* first_invalid, int32_t* n_points) {
+  if (!p || n < 0 || (n > 0 && (!from_rows || !to_rows || !first_invalid))) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  MarginCfg mg;
+  bool on;
+  if (int st = margin_cfg(p, margin, check_self, check_map, &mg, &on)) return st;
+  if (n == 0) return SMP_OK;
+  if (check_map && !p->have_scene) return SMP_ERR_ARG;
+  return check_edges_body(p, from_rows, to_rows, n, Checks{check_self, check_map, on ? &mg : nullptr}, first_invalid,
+                          n_points);
+}
+
+// The predicate on n configurations (row-major n x 8): clear[i] = 1 iff configuration i is clear.
+int smp_check_configs_margin(smp_planner* p, const double* q_rows, int64_t n, int check_self, int check_map,
+                             const smp_margin* margin, uint8_t* clear) {
+  if (!p || n < 0 || (n > 0 && (!q_rows || !clear))) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  MarginCfg mg;
+  bool on;
+  if (int st = margin_cfg(p, margin, check_self, check_map, &mg, &on)) return st;
+  if (on && check_map && !p->have_scene) return SMP_ERR_ARG;
+  if (n == 0) return SMP_OK;
+  if (on && n > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
+  if (on && !finite_rows(q_rows, n)) return SMP_ERR_ARG;
+  double ms = 0;
+  const int st = check_rows(p, Checks{check_self, check_map, on ? &mg : nullptr}, q_rows, n, clear, &ms);
+  if (st == SMP_OK) p->last_check_ms = ms;
+  return st;
+}
+
 // Path shortcutting: every candidate waypoint pair checked densely in one launch, then the cheapest route through the
 // valid pairs (host, fp64), with the via nodes of the chosen edges inserted.
-int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map, int window,
-                      double** out_waypoints, int64_t* n_out, smp_shortcut_info* info) {
+static int shortcut_body(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map, int window,
+                         const smp_margin* margin, double** out_waypoints, int64_t* n_out, smp_shortcut_info* info) {
   if (!p || !waypoints || !out_waypoints || !n_out || k < 2) return SMP_ERR_ARG;
   const auto t_begin = std::chrono::steady_clock::now();
   *out_waypoints = nullptr;
@@ -122,6 +236,10 @@ int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int ch
     info->first_blocked = -1;
   }
   if (int b_ = busy_check(p)) return b_;
+  MarginCfg mg;
+  bool on;
+  if (int st = margin_cfg(p, margin, check_self, check_map, &mg, &on)) return st;
+  const Checks ck{check_self, check_map, on ? &mg : nullptr};
   if (check_map && !p->have_scene) return SMP_ERR_ARG;
   if (k > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   const int64_t w = shortcut_window(k, window);
@@ -131,7 +249,7 @@ int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int ch
   if (!shortcut_edges(edge_rule(p), waypoints, k, w, &edges)) return SMP_ERR_ARG;
   std::vector<int> first;
   double ms = 0;
-  const int st = run_edges(p, edges, check_self, check_map, first, &ms);
+  const int st = run_edges(p, edges, ck, first, &ms);
   if (st != SMP_OK) return st;
   smp_shortcut_info s;
   const std::vector<EdgeDev> route = shortcut_route(waypoints, k, w, edges, first, &s);
@@ -149,19 +267,34 @@ int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int ch
   return rc;
 }
 
+int smp_shortcut_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map, int window,
+                      double** out_waypoints, int64_t* n_out, smp_shortcut_info* info) {
+  return shortcut_body(p, waypoints, k, check_self, check_map, window, nullptr, out_waypoints, n_out, info);
+}
+
+int smp_shortcut_path_margin(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                             int window, const smp_margin* margin, double** out_waypoints, int64_t* n_out,
+                             smp_shortcut_info* info) {
+  return shortcut_body(p, waypoints, k, check_self, check_map, window, margin, out_waypoints, n_out, info);
+}
+
 // ------------------------------------------------------------------------------------------ path repair
 static_assert(sizeof(smp_detour) == sizeof(DetourDev), "smp_detour is the kernel's record");
 
-// One detours_kernel launch: out[g * samples + s] for the gaps of the table.
+// One launch of detour items: out[g * samples + s] for the gaps of the table.
 static int run_detours(smp_planner* p, const std::vector<GapDev>& gaps, int samples, double h, uint64_t seed,
-                       uint32_t round, int self, int map, DetourDev* out, double* kernel_ms) {
+                       uint32_t round, const Checks& ck, DetourDev* out, double* kernel_ms) {
   const size_t n_items = gaps.size() * (size_t)samples;
-  const DetourArgs a{(int)n_items, samples, p->params.num_traj_segments, SMP_EDGE_MAX_POINTS, self,
-                     map && p->have_scene, round, seed, p->params.step_factor, h};
+  const DetourArgs a{(int)n_items, samples, p->params.num_traj_segments, SMP_EDGE_MAX_POINTS, ck.self,
+                     ck.map && p->have_scene, round, seed, p->params.step_factor, h};
   return run_pass(
       p, n_items, [&] { return upload(p, p->d_gaps, gaps.data(), gaps.size()); },
       [&](int grid) {
-        launch_detours(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_gaps.p, a, p->d_ecounter.p, p->d_detours.p);
+        if (ck.mg)
+          launch_margin_detours(grid, p->stream, p->d_rb, p->sc, p->d_mc, *ck.mg, p->d_gaps.p, a, p->d_ecounter.p,
+                                p->d_detours.p);
+        else
+          launch_detours(grid, p->stream, p->d_rb, p->sc, p->d_mc, p->d_gaps.p, a, p->d_ecounter.p, p->d_detours.p);
       },
       p->d_detours, out, n_items, kernel_ms);
 }
@@ -174,18 +307,16 @@ static GapDev make_gap(const double* a, const double* b, unsigned g) {
   return d;
 }
 
-static bool finite_rows(const double* rows, int64_t n) {
-  for (int64_t i = 0; i < n * NJ; ++i)
-    if (!std::isfinite(rows[i])) return false;
-  return true;
-}
-
-int smp_sample_detours(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps, int samples,
-                       double half_width, uint64_t seed, uint32_t round, int check_self, int check_map,
-                       smp_detour* out) {
+static int sample_detours_body(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps,
+                               int samples, double half_width, uint64_t seed, uint32_t round, int check_self,
+                               int check_map, const smp_margin* margin, smp_detour* out) {
   if (!p || n_gaps < 0 || samples < 1 || !std::isfinite(half_width) || (n_gaps > 0 && (!from_rows || !to_rows || !out)))
     return SMP_ERR_ARG;
   if (int b_ = busy_check(p)) return b_;
+  MarginCfg mg;
+  bool on;
+  if (int st = margin_cfg(p, margin, check_self, check_map, &mg, &on)) return st;
+  const Checks ck{check_self, check_map, on ? &mg : nullptr};
   if (n_gaps == 0) return SMP_OK;
   if (check_map && !p->have_scene) return SMP_ERR_ARG;
   if (n_gaps > SMP_EDGE_TABLE_MAX || n_gaps * (int64_t)samples > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
@@ -193,11 +324,24 @@ int smp_sample_detours(smp_planner* p, const double* from_rows, const double* to
   std::vector<GapDev> gaps((size_t)n_gaps);
   for (int64_t g = 0; g < n_gaps; ++g) gaps[(size_t)g] = make_gap(from_rows + g * NJ, to_rows + g * NJ, (unsigned)g);
   double ms = 0;
-  const int st = run_detours(p, gaps, samples, half_width, seed, round, check_self, check_map,
-                             reinterpret_cast<DetourDev*>(out), &ms);
+  const int st = run_detours(p, gaps, samples, half_width, seed, round, ck, reinterpret_cast<DetourDev*>(out), &ms);
   if (st != SMP_OK) return st;
   p->last_check_ms = ms;
   return SMP_OK;
+}
+
+int smp_sample_detours(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps, int samples,
+                       double half_width, uint64_t seed, uint32_t round, int check_self, int check_map,
+                       smp_detour* out) {
+  return sample_detours_body(p, from_rows, to_rows, n_gaps, samples, half_width, seed, round, check_self, check_map,
+                             nullptr, out);
+}
+
+int smp_sample_detours_margin(smp_planner* p, const double* from_rows, const double* to_rows, int64_t n_gaps,
+                              int samples, double half_width, uint64_t seed, uint32_t round, int check_self,
+                              int check_map, const smp_margin* margin, smp_detour* out) {
+  return sample_detours_body(p, from_rows, to_rows, n_gaps, samples, half_width, seed, round, check_self, check_map,
+                             margin, out);
 }
 
 void smp_repair_opts_default(smp_repair_opts* o) {
@@ -209,8 +353,9 @@ void smp_repair_opts_default(smp_repair_opts* o) {
 
 // Path repair: the waypoints and the adjacent edges checked, the blocked stretches gathered into gaps between valid
 // waypoints, and each gap bridged by the cheapest free one-via detour of the first round that has one.
-int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
-                    const smp_repair_opts* opts, double** out_waypoints, int64_t* n_out, smp_repair_info* info) {
+static int repair_body(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                       const smp_repair_opts* opts, const smp_margin* margin, double** out_waypoints, int64_t* n_out,
+                       smp_repair_info* info) {
   if (!p || !waypoints || !out_waypoints || !n_out || k < 2) return SMP_ERR_ARG;
   const auto t_begin = std::chrono::steady_clock::now();
   *out_waypoints = nullptr;
@@ -224,6 +369,10 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
   if (opts) o = *opts;
   if (o.samples < 1 || o.rounds < 1 || o.rounds > 32) return SMP_ERR_ARG;
   if (int b_ = busy_check(p)) return b_;
+  MarginCfg mg;
+  bool on;
+  if (int st = margin_cfg(p, margin, check_self, check_map, &mg, &on)) return st;
+  const Checks ck{check_self, check_map, on ? &mg : nullptr};
   if (check_map && !p->have_scene) return SMP_ERR_ARG;
   if (k > SMP_EDGE_TABLE_MAX) return SMP_ERR_CAPACITY;
   if (!finite_rows(waypoints, k)) return SMP_ERR_ARG;
@@ -233,12 +382,9 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
   // 1. validity of the waypoints and of the adjacent edges
   std::vector<uint8_t> valid((size_t)k);
   {
-    std::vector<double> soa((size_t)k * NJ);
-    for (int64_t i = 0; i < k; ++i)
-      for (int j = 0; j < NJ; ++j) soa[(size_t)j * k + i] = W(i)[j];
-    const int st = smp_check_configs(p, soa.data(), k, check_self, check_map, valid.data());
+    const int st = check_rows(p, ck, waypoints, k, valid.data(), &ms);
     if (st != SMP_OK) return st;
-    kernel_ms += p->last_check_ms;
+    kernel_ms += ms;
   }
   if (!valid[0]) return SMP_ERR_START_INVALID;
   if (!valid[(size_t)(k - 1)]) return SMP_ERR_GOAL_INVALID;
@@ -247,7 +393,7 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
     if (!make_edge(rule, W(i), W(i + 1), &edges[(size_t)i])) return SMP_ERR_ARG;
   std::vector<int> first;
   {
-    const int st = run_edges(p, edges, check_self, check_map, first, &ms);
+    const int st = run_edges(p, edges, ck, first, &ms);
     if (st != SMP_OK) return st;
     kernel_ms += ms;
   }
@@ -268,7 +414,7 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
       if (gaps[(size_t)g].open) table.push_back(make_gap(W(gaps[(size_t)g].l), W(gaps[(size_t)g].r), (unsigned)g));
     items.resize(table.size() * (size_t)o.samples);
     const double h = std::ldexp(p->params.step_factor, rho);
-    const int st = run_detours(p, table, o.samples, h, o.seed, (uint32_t)rho, check_self, check_map, items.data(), &ms);
+    const int st = run_detours(p, table, o.samples, h, o.seed, (uint32_t)rho, ck, items.data(), &ms);
     if (st != SMP_OK) return st;
     kernel_ms += ms;
     ++r.rounds_used;
@@ -296,6 +442,17 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
   }
   p->last_check_ms = kernel_ms;
   return rc;
+}
+
+int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                    const smp_repair_opts* opts, double** out_waypoints, int64_t* n_out, smp_repair_info* info) {
+  return repair_body(p, waypoints, k, check_self, check_map, opts, nullptr, out_waypoints, n_out, info);
+}
+
+int smp_repair_path_margin(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
+                           const smp_repair_opts* opts, const smp_margin* margin, double** out_waypoints, int64_t* n_out,
+                           smp_repair_info* info) {
+  return repair_body(p, waypoints, k, check_self, check_map, opts, margin, out_waypoints, n_out, info);
 }
 
 void smp_buffer_free(void* buffer) { std::free(buffer); }

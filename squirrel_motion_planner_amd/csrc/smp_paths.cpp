@@ -155,4 +155,18 @@ double* route_rows(const std::vector<EdgeDev>& route, int num_traj_segments, int
   return out;
 }
 
+double margin_threshold(double r, double m) {
+  auto within = [&](double S) {
+    const double t = std::sqrt(S);
+    return t - r <= m;
+  };
+  double S = (r + m) * (r + m);
+  if (within(S)) {
+    for (double up = std::nextafter(S, HUGE_VAL); within(up); up = std::nextafter(S, HUGE_VAL)) S = up;
+  } else {
+    do S = std::nextafter(S, 0.0); while (!within(S));  // (within(0): -r <= m)
+  }
+  return S;
+}
+
 }  // namespace smp

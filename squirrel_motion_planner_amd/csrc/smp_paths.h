@@ -66,4 +66,10 @@ bool repaired_route(const EdgeRule& r, const double* waypoints, int64_t k, const
 // edge's end.  A malloc'd rows x NJ buffer (smp_buffer_free); nullptr, and *rows untouched, if the allocation fails.
 double* route_rows(const std::vector<EdgeDev>& route, int num_traj_segments, int64_t* rows);
 
+// The margin checks' threshold on a squared distance (include/smp_gpu.h "Margin checks"): the largest double S with
+// fl(fl(sqrt(S)) - r) <= m, for a radius r >= 0 (0 for a primitive) and a margin m > 0, both finite.  sqrt and the
+// subtraction are monotone, so a cell at squared distance s has a term <= m iff s <= S: the kernel compares squares and
+// takes no square root per cell.  Found from fl((r + m)^2) by steps of one ulp.
+double margin_threshold(double r, double m);
+
 }  // namespace smp

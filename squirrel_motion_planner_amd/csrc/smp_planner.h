@@ -14,6 +14,7 @@
 #include "smp_pass.h"
 #include "smp_host.h"
 #include "smp_ik.h"
+#include "smp_margin.h"
 #include "smp_plan.h"
 #include "smp_types.h"
 
@@ -123,6 +124,9 @@ struct smp_planner {
   smp::DBuf<double> d_clq;
   smp::DBuf<smp::ClearDev> d_clc;
   smp::DBuf<smp::EdgeClearDev> d_cle;
+  // margin checks (smp_check_configs_margin): per-configuration results; the rows are d_clq, the other tables those of
+  // the plain passes
+  smp::DBuf<uint8_t> d_mclear;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_check_ms = 0, last_plan_ms = 0;
   int64_t last_plan_launches = 0;

@@ -279,58 +279,85 @@ class GpuPlanner:
                                        ctypes.byref(first)), "smp_check_sequence")
         return first.value
 
-    def check_edges(self, frm, to, check_self=True, check_map=True):
+    def check_clear(self, q, check_self=True, check_map=True, margin=None):
+        """smp_check_configs_margin: 1 per configuration that is valid and farther than margin = (map, self) metres
+        from the map and from self-collision (include/smp_gpu.h "Margin checks"), else 0.  margin=None is (0, 0): the
+        validity check."""
+        q = np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1, 8))
+        out = np.zeros(len(q), np.uint8)
+        check(lib().smp_check_configs_margin(self.h, q.ctypes.data_as(_pd), len(q), int(check_self), int(check_map),
+                                             _margin(margin), out.ctypes.data_as(ctypes.c_void_p)),
+              "smp_check_configs_margin")
+        return out
+
+    def check_edges(self, frm, to, check_self=True, check_map=True, margin=None):
         """Batched isEdgeValid (birrt_star.cpp:6864-6895) at the density rule of smp_check_edges: (first_invalid,
-        n_points) per edge frm[i] -> to[i]; first_invalid is the index of the first colliding point, -1 if free."""
+        n_points) per edge frm[i] -> to[i]; first_invalid is the index of the first colliding point, -1 if free.
+        margin = (map, self): smp_check_edges_margin, the first point that is not clear at those margins."""
         a, b = _edge_rows("check_edges", frm, to)
         first = np.zeros(len(a), np.int64)
         npts = np.zeros(len(a), np.int32)
-        check(lib().smp_check_edges(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(check_self),
-                                    int(check_map), first.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                    npts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "smp_check_edges")
+        args = (first.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), npts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        head = (self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(check_self), int(check_map))
+        if margin is None:
+            check(lib().smp_check_edges(*head, *args), "smp_check_edges")
+        else:
+            check(lib().smp_check_edges_margin(*head, _margin(margin), *args), "smp_check_edges_margin")
         return first, npts
 
-    def shortcut_path(self, path, check_self=True, check_map=True, window=0):
+    def shortcut_path(self, path, check_self=True, check_map=True, window=0, margin=None):
         """smp_shortcut_path: every waypoint pair within `window` (0: all pairs) checked as a dense edge in one launch,
         the cheapest route through the valid ones, via nodes inserted.  Returns (path (m, 8), info dict); a blocked
-        path raises SmpError with status SMP_ERR_NO_SOLUTION, its `info` attribute holding the dict."""
+        path raises SmpError with status SMP_ERR_NO_SOLUTION, its `info` attribute holding the dict.
+        margin = (map, self): smp_shortcut_path_margin, the route through the pairs that are clear at those margins."""
         w = np.ascontiguousarray(np.asarray(path, np.float64).reshape(-1, 8))
         out = _pd()
         n_out = ctypes.c_int64()
         info = L.ShortcutInfo()
-        rc = lib().smp_shortcut_path(self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map),
-                                     int(window), ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
-        return _returned_path("smp_shortcut_path", rc, out, n_out, info)
+        head = (self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map), int(window))
+        tail = (ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
+        if margin is None:
+            return _returned_path("smp_shortcut_path", lib().smp_shortcut_path(*head, *tail), out, n_out, info)
+        rc = lib().smp_shortcut_path_margin(*head, _margin(margin), *tail)
+        return _returned_path("smp_shortcut_path_margin", rc, out, n_out, info)
 
-    def sample_detours(self, frm, to, samples, half_width, seed=1, round=0, check_self=True, check_map=True):
+    def sample_detours(self, frm, to, samples, half_width, seed=1, round=0, check_self=True, check_map=True,
+                       margin=None):
         """smp_sample_detours: for every gap frm[g] -> to[g], `samples` one-via detours drawn around the gap's centre
         within `half_width` and both legs of each checked densely, one launch.  Returns a dict of v (G, S, 8), M1, M2
-        and free (G, S)."""
+        and free (G, S).  margin = (map, self): smp_sample_detours_margin, free = both legs clear at those margins."""
         a, b = _edge_rows("sample_detours", frm, to)
         n = len(a) * max(int(samples), 0)
         out = (L.Detour * max(n, 1))()
-        check(lib().smp_sample_detours(self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(samples),
-                                       float(half_width), int(seed), int(round), int(check_self), int(check_map), out),
-              "smp_sample_detours")
+        head = (self.h, a.ctypes.data_as(_pd), b.ctypes.data_as(_pd), len(a), int(samples), float(half_width), int(seed),
+                int(round), int(check_self), int(check_map))
+        if margin is None:
+            check(lib().smp_sample_detours(*head, out), "smp_sample_detours")
+        else:
+            check(lib().smp_sample_detours_margin(*head, _margin(margin), out), "smp_sample_detours_margin")
         rec = np.frombuffer(out, dtype=np.dtype([("v", np.float64, 8), ("M1", np.int32), ("M2", np.int32),
                                                  ("free", np.int32), ("pad", np.int32)]), count=n)
         shape = (len(a), int(samples))
         return dict(v=rec["v"].reshape(shape + (8,)).copy(), M1=rec["M1"].reshape(shape).copy(),
                     M2=rec["M2"].reshape(shape).copy(), free=rec["free"].reshape(shape).copy())
 
-    def repair_path(self, path, check_self=True, check_map=True, samples=256, rounds=4, seed=1):
+    def repair_path(self, path, check_self=True, check_map=True, samples=256, rounds=4, seed=1, margin=None):
         """smp_repair_path: the blocked stretches of `path` gathered into gaps between valid waypoints and each bridged
         by the cheapest free one-via detour, the half width doubling per round.  Returns (path (m, 8), info dict) with
         the via nodes of every edge inserted; gaps that stay open raise SmpError with status SMP_ERR_NO_SOLUTION, its
-        `info` attribute holding the dict (as every other failure does)."""
+        `info` attribute holding the dict (as every other failure does).  margin = (map, self):
+        smp_repair_path_margin, "valid / free" read as "clear at those margins"."""
         w = np.ascontiguousarray(np.asarray(path, np.float64).reshape(-1, 8))
         out = _pd()
         n_out = ctypes.c_int64()
         info = L.RepairInfo()
         opts = L.RepairOpts(int(samples), int(rounds), int(seed))
-        rc = lib().smp_repair_path(self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map),
-                                   ctypes.byref(opts), ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
-        return _returned_path("smp_repair_path", rc, out, n_out, info)
+        head = (self.h, w.ctypes.data_as(_pd), len(w), int(check_self), int(check_map), ctypes.byref(opts))
+        tail = (ctypes.byref(out), ctypes.byref(n_out), ctypes.byref(info))
+        if margin is None:
+            return _returned_path("smp_repair_path", lib().smp_repair_path(*head, *tail), out, n_out, info)
+        rc = lib().smp_repair_path_margin(*head, _margin(margin), *tail)
+        return _returned_path("smp_repair_path_margin", rc, out, n_out, info)
 
     def clearance(self, q, max_dist=0.3, with_self=True, with_map=True):
         """smp_clearance_configs: distance of every configuration to the map (capped at max_dist) and to self-collision,
@@ -580,6 +607,14 @@ IK_DEVIATION = [(-0.005, 0.005)] * 3 + [(-0.025, 0.025)] * 3
 _CALL_FAILURES = (L.SMP_ERR_HIP, L.SMP_ERR_NO_DEVICE, L.SMP_ERR_PARSE)
 
 
+def _margin(margin):
+    """smp_margin* of a (map, self) pair; None is the NULL margin."""
+    if margin is None:
+        return None
+    m, s = margin
+    return ctypes.byref(L.Margin(float(m), float(s)))
+
+
 def _edge_rows(what, frm, to):
     """The contiguous (n, 8) start and end rows of a table of edges or gaps."""
     a = np.ascontiguousarray(np.asarray(frm, np.float64).reshape(-1, 8))
@@ -685,16 +720,26 @@ class BiRRTstarPlanner:
         f = int(first[0])
         return f < 0, (int(npts[0]) - 1 if f < 0 else max(f - 1, 0))
 
-    def shortcutTrajectory(self, trajectory, check_self_collision=True, check_map_collision=True, window=0):
+    def isEdgeClear(self, start_conf, end_conf, margin, check_self_collision=True, check_map_collision=True):
+        """Not in the reference: isEdgeValid with a safety margin = (map, self) in metres (GpuPlanner.check_edges):
+        (clear, last_clear_node_idx), the index read as isEdgeValid's."""
+        first, npts = self._gpu.check_edges([start_conf], [end_conf], check_self_collision, check_map_collision,
+                                            margin=margin)
+        f = int(first[0])
+        return f < 0, (int(npts[0]) - 1 if f < 0 else max(f - 1, 0))
+
+    def shortcutTrajectory(self, trajectory, check_self_collision=True, check_map_collision=True, window=0,
+                           margin=None):
         """Shortens `trajectory` (a list of 8-value poses, e.g. getJointTrajectoryRef()) in place
         (GpuPlanner.shortcut_path); False, trajectory untouched, when the path is blocked or has fewer than two poses.
         The node would call it between getJointTrajectoryRef and normalizeTrajectory.  `shortcut_info` keeps the
-        call's counts, costs and timing."""
+        call's counts, costs and timing.  margin = (map, self) in metres keeps the route that far from the map and
+        from self-collision (GpuPlanner.shortcut_path's margin)."""
         if len(trajectory) < 2:
             return False
         try:
             path, self.shortcut_info = self._gpu.shortcut_path(trajectory, check_self_collision, check_map_collision,
-                                                               window)
+                                                               window, margin=margin)
         except L.SmpError as e:
             if e.status != L.SMP_ERR_NO_SOLUTION:
                 raise
@@ -704,17 +749,19 @@ class BiRRTstarPlanner:
         return True
 
     def repairTrajectory(self, trajectory, check_self_collision=True, check_map_collision=True, samples=256,
-                         rounds=4, seed=1):
+                         rounds=4, seed=1, margin=None):
         """Repairs `trajectory` (a list of 8-value poses, e.g. getJointTrajectoryRef()) in place
         (GpuPlanner.repair_path): its blocked stretches are bridged by one-via detours and the via nodes of every edge
         are inserted.  False, trajectory untouched, when a stretch stays blocked, an end pose is invalid or there are
         fewer than two poses.  The node would call it between getJointTrajectoryRef and shortcutTrajectory.
-        `repair_info` keeps the call's counts, costs and timing."""
+        `repair_info` keeps the call's counts, costs and timing.  margin = (map, self) in metres repairs every stretch
+        that is not clear at those margins (GpuPlanner.repair_path's margin); repair with a margin, then shortcut with
+        the same one."""
         if len(trajectory) < 2:
             return False
         try:
             path, self.repair_info = self._gpu.repair_path(trajectory, check_self_collision, check_map_collision,
-                                                           samples, rounds, seed)
+                                                           samples, rounds, seed, margin=margin)
         except L.SmpError as e:
             if e.status not in (L.SMP_ERR_NO_SOLUTION, L.SMP_ERR_START_INVALID, L.SMP_ERR_GOAL_INVALID):
                 raise
