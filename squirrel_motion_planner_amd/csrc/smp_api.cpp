@@ -14,20 +14,13 @@
 #include <string>
 #include <vector>
 
+#include "smp_kernels.h"
 #include "smp_math.h"
 #include "smp_planner.h"
 #include "smp_scene.h"
 
 namespace smp {
-void launch_check(int ct, int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const double* q,
-                  long long n, int self, int map, uint8_t* valid, unsigned long long* prof);
-__global__ void plan_kernel(const RobotDev* rb, SceneDev sc, const MapCfg* mc, QueryDev* qs, int nq, int scout_base,
-                            int helper_base, int iters);
-__global__ void path_kernel(QueryDev* qs, int* counts);
-size_t check_kernels_private_bytes();
 size_t ik_kernels_private_bytes();
-void launch_collisions(hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const double* q, int map,
-                       uint8_t* link_map, uint8_t* pair_self);
 void launch_ik(bool search, int n, hipStream_t st, const RobotDev* rb, const IkTaskDev* tasks, IkOutDev* out,
                SceneDev sc, const MapCfg* mc, int self, int map, int* best);
 }  // namespace smp

@@ -13,16 +13,9 @@
 #include <thread>
 #include <vector>
 
+#include "smp_kernels.h"
 #include "smp_planner.h"
 #include "smp_provision.h"
-
-namespace smp {
-__global__ void plan_kernel(const RobotDev* rb, SceneDev sc, const MapCfg* mc, QueryDev* qs, int nq, int scout_base,
-                            int helper_base, int iters);
-__global__ void path_kernel(QueryDev* qs, int* counts);
-__global__ void path_edges_kernel(const QueryDev* qs, int q, int ns, int ng, double* out);
-__global__ void boards_reset_kernel(const QueryDev* qs, int ns);
-}  // namespace smp
 
 using namespace smp;
 
@@ -42,11 +35,6 @@ static int resident_slots(smp_planner* p) {
   p->slots_cache = p->num_cus * std::max(1, occ_plan);
   return std::max(1, p->slots_cache / std::max(1, p->slot_share));
 }
-
-extern "C" int smp_debug_bounds(int* out);
-#ifdef SMP_RING_CHECK
-extern "C" void smp_ringchk_dump();
-#endif
 
 // ------------------------------------------------------------------------------------------ planning
 // C = H * diag(1, .., 1, det H), H = I - 2 v v^T / v^T v, v = e1 - a (DESIGN.md "Informed sampling");
@@ -516,8 +504,8 @@ static int plan_launch_loop(PlanCall& c) {
     if (k.bounds) {
       int dbg[8];
       if (smp_debug_bounds(dbg) == 0 && dbg[0])
-        std::fprintf(stderr, "[smp] bounds: line %d id %d block %d tree %d limit %d (launch %lld)\n", dbg[0], dbg[1],
-                     dbg[2], dbg[3], dbg[4], (long long)c.launches);
+        std::fprintf(stderr, "[smp] bounds: %s:%d id %d block %d tree %d limit %d (launch %lld)\n", site_file(dbg[0]),
+                     site_line(dbg[0]), dbg[1], dbg[2], dbg[3], dbg[4], (long long)c.launches);
     }
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));

@@ -5,22 +5,8 @@
 #include <cstring>
 #include <vector>
 
+#include "smp_kernels.h"
 #include "smp_planner.h"
-
-namespace smp {
-void launch_check(int ct, int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, const double* q,
-                  long long n, int self, int map, uint8_t* valid, unsigned long long* prof);
-__global__ void sincos_kernel(const double* x, int n, double* s, double* c);
-__global__ void u01_kernel(unsigned long long seed, unsigned query, const uint32_t* ctr, int n, double* out);
-__global__ void fk_kernel(const RobotDev* rb, const double* q, int n, double* frames, double* eez);
-__global__ void sqrt_div_kernel(const double* a, const double* b, int n, double* sq, double* dv);
-__global__ void near_probe_kernel(const double* tq, const double* tcost, int cap, int n, const double* queries,
-                                  const int* excl, int m, double r, int reps, int* nn, int* nk, int* lo, int* hi,
-                                  unsigned long long* ticks, const float* tqf);
-__global__ void near_probe_inl_kernel(const double* tq, const double* tcost, int cap, int n, const double* queries,
-                                      const int* excl, int m, double r, int reps, int* nn, int* nk, int* lo, int* hi,
-                                      unsigned long long* ticks, const float* tqf);
-}  // namespace smp
 
 using namespace smp;
 

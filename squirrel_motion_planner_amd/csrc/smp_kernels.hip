@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "smp_collide.h"
+#include "smp_kernels.h"
 #include "smp_math.h"
 #include "smp_plan.h"
 #include "smp_types.h"
@@ -290,15 +291,10 @@ __device__ __forceinline__ unsigned long long merge_key(const MergeLds& M, int s
 }
 // LDS of job mode (leader and helper kernel): the published job + one job tile.
 struct JobLds {
-#ifdef SMP_NO_SCAN_UNION
-  ScanLds scan;
-  WideLds T;
-#else
   union {
     ScanLds scan;                          // helper: its slice of a scan job
     WideLds T;                             // one job tile (collide_wide)
   };
-#endif
   double tq[TILE_CT_MAX][NJ];
   double start[MAXE][NJ], step[MAXE][NJ];  // the job's edges (needed edges of the batch, compacted)
   unsigned words[JOB_WORDS];               // helper: the payload words as received
@@ -496,66 +492,11 @@ struct Ctx {
   QueryDev Q;
 };
 
-// SMP_TRACE builds (tools/trace_probe.py): thread 0 of the leader and of the scouts appends (role, source line,
-// device clock) records for the iterations [SMP_TRACE_IT0, SMP_TRACE_IT1) of query 0; smp_debug_tlog reads them.
-#ifdef SMP_TRACE
-#ifndef SMP_TRACE_IT0
-#define SMP_TRACE_IT0 3000
-#endif
-#ifndef SMP_TRACE_IT1
-#define SMP_TRACE_IT1 3040
-#endif
-constexpr unsigned TLOG_CAP = 1u << 18, TLOG_ROLE = TLOG_CAP / 4;  // records per role (0 leader, 1-2 scouts)
-__device__ unsigned long long g_tlog[TLOG_CAP];
-__device__ unsigned g_tlog_n[4];
-// No atomics: each workgroup keeps its role's record count in LDS (loaded at launch start by tlog_begin) and
-// stores it back after every record (plain stores, nothing waited on), so tracing adds ~0.1 us per record.
-#define TR()                                                                                                  \
-  if (threadIdx.x == 0 && g_L.tit >= SMP_TRACE_IT0 && g_L.tit < SMP_TRACE_IT1 && g_L.tn < TLOG_ROLE) {        \
-    g_tlog[g_L.trole * TLOG_ROLE + g_L.tn] =                                                                   \
-        ((unsigned long long)g_L.trole << 62) | ((unsigned long long)((g_L.tit - SMP_TRACE_IT0) & 0xff) << 54) | \
-        ((unsigned long long)(__LINE__ & 0x3fff) << 40) | (wall_clock64() & 0xffffffffffull);                  \
-    g_tlog_n[g_L.trole] = ++g_L.tn;                                                                            \
-  }
-// The barriers of a leader iteration, counted by thread 0 (every __syncthreads() below this line) and logged at the
-// iteration's end as a record whose line field is TR_BAR0 + the count (trace_probe.py prints them apart).
-constexpr int TR_BAR0 = 16000;
-#define __syncthreads()                 \
-  do {                                  \
-    if (threadIdx.x == 0) ++g_L.tbar;   \
-    __syncthreads();                    \
-  } while (0)
-#define TR_BARRIERS()                                                                                          \
-  if (threadIdx.x == 0 && g_L.tit >= SMP_TRACE_IT0 && g_L.tit < SMP_TRACE_IT1 && g_L.tn < TLOG_ROLE) {        \
-    g_tlog[g_L.trole * TLOG_ROLE + g_L.tn] =                                                                   \
-        ((unsigned long long)g_L.trole << 62) | ((unsigned long long)((g_L.tit - SMP_TRACE_IT0) & 0xff) << 54) | \
-        ((unsigned long long)((TR_BAR0 + min(g_L.tbar, 383)) & 0x3fff) << 40) | (wall_clock64() & 0xffffffffffull); \
-    g_tlog_n[g_L.trole] = ++g_L.tn;                                                                            \
-  }
-#else
-#define TR()
-#define TR_BARRIERS()
-#endif
-
-// Phase clocks (thread 0, s_memrealtime ticks): where an iteration spends its time.
-enum { P_SAMPLE, P_NN, P_EXPAND, P_NEAR, P_CHOOSE, P_REWIRE, P_CONNECT, P_TILES, P_NTILES, P_COSTS, P_VIA, P_NVIA,
-       P_TFK, P_TCHAIN, P_TCENTRE, P_TTEST, P_XEXPAND, P_XCHOOSE, P_XREWIRE, P_XCONNECT };
-// Phase clocks read the device wall clock (s_memrealtime, a scalar memory round trip each); SMP_NOCLK builds
-// compile them out of the phase / stage accounting (the timeouts and the planning clock keep theirs).
-#ifdef SMP_NOCLK
-__device__ __forceinline__ unsigned long long pclk() { return 0; }
-#else
-__device__ __forceinline__ unsigned long long pclk() { return wall_clock64(); }
-#endif
-#define PROF_BEGIN() unsigned long long _pt = threadIdx.x == 0 ? pclk() : 0
-#ifdef SMP_DETAIL_PROF  // thread-0 clocks of serial sections into prof[28..31] (perf_probe.py SMP_DETAIL_PROF=1)
-#define DETAIL_BEGIN(v) const unsigned long long v = threadIdx.x == 0 ? wall_clock64() : 0
-#define DETAIL_END(v, k) if (threadIdx.x == 0) g_L.S.prof[k] += wall_clock64() - v
-#else
-#define DETAIL_BEGIN(v)
-#define DETAIL_END(v, k)
-#endif
-#define PROF_END(k) if (threadIdx.x == 0) { g_L.S.prof[k] += pclk() - _pt; }
+// Everything that measures or checks (trace log, phase clocks, the profiling variants, the bounds check): in trace
+// builds it redefines __syncthreads() to count every barrier below this line.
+}  // namespace smp
+#include "smp_plan_prof.h"
+namespace smp {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 // Block-uniform control value read from LDS, made provably wave-uniform (a scalar register): every loop
@@ -658,24 +599,12 @@ __device__ __forceinline__ bool same8(const double* a, const double* b) {
 }
 
 // --------------------------------------------------------------------------------------- node access
-// SMP_BOUNDS builds (debugging): out-of-range node ids are recorded in g_dbg (first one: source line, id, block,
-// tree) and replaced by 0 instead of being dereferenced; smp_debug_bounds() reads the record.
-#ifdef SMP_BOUNDS
-__device__ int g_dbg[8];
-#define BCHK(id, lim, line, t)                                                                          \
-  if ((unsigned)(id) >= (unsigned)(lim)) {                                                             \
-    if (atomicCAS(&g_dbg[0], 0, (line)) == 0) { g_dbg[1] = (id); g_dbg[2] = blockIdx.x; g_dbg[3] = (t); g_dbg[4] = (lim); } \
-    id = 0;                                                                                            \
-  }
-#else
-#define BCHK(id, lim, line, t)
-#endif
-#define load_node(C, t, id, o) load_node_at(C, t, id, o, __LINE__)
-__device__ __forceinline__ void load_node_at(const Ctx& C, int t, int id, NodeRef* o, int line) {
+#define load_node(C, t, id, o) load_node_at(C, t, id, o, SMP_SITE)
+__device__ __forceinline__ void load_node_at(const Ctx& C, int t, int id, NodeRef* o, int site) {
   const TreeDev& T = C.Q.tr[t];
   const int cap = g_L.S.cap;  // (the leader and scouts stage their QState in LDS: no dependent global load for it)
-  BCHK(id, cap, line, t);
-  (void)line;
+  BCHK(id, cap, site, t);
+  (void)site;
   for (int j = 0; j < NJ; ++j) o->q[j] = T.q[(size_t)j * cap + id];
   for (int k = 0; k < 3; ++k) o->c[k] = T.cost[(size_t)k * cap + id];
   o->id = id;
@@ -1816,21 +1745,6 @@ __device__ __forceinline__ void slice_near_inl(gcdptr tq, gcdptr tc, int cap, in
 //      are gathered in an LDS buffer (one atomic per wave and list) and every entry is ranked by counting the
 //      entries ahead of it (2-4 lanes per entry): the entries of rank < K are the new running list.
 // A buffer that would exceed NEAR_BUF entries (ties, clustered costs) sends the call to near_set_stream.
-#ifdef SMP_NEAR_PROF  // clocks of the barrier-separated steps into prof[20..24]; path counts in prof[26], prof[27]
-#define NEAR_CLOCK(k)                                                                    \
-  if (threadIdx.x == 0) {                                                                \
-    const unsigned long long _t = wall_clock64();                                        \
-    if (k > 0) g_L.S.prof[19 + k] += _t - _tn;                                           \
-    _tn = _t;                                                                            \
-  }
-#define NEAR_COUNT(k) if (threadIdx.x == 0) g_L.S.prof[k]++
-#elif defined(SMP_TRACE)
-#define NEAR_CLOCK(k) TR()
-#define NEAR_COUNT(k)
-#else
-#define NEAR_CLOCK(k)
-#define NEAR_COUNT(k)
-#endif
 
 // NN: also the nearest node of q over the whole tree (no exclusion; nearest()'s answer) in g_L.fnn_d / fnn_id -- connect's
 // two scans of x_new in tree_B in one pass (no scout record then: spec must be false).
@@ -1925,9 +1839,7 @@ __device__ __forceinline__ bool near_set_rec(const Ctx& C, int t, const double* 
 
 template <int K, bool NN = false>
 __device__ void near_set(const Ctx& C, int t, const double* q, int excl, bool spec = false) {
-#ifdef SMP_NEAR_PROF
-  unsigned long long _tn = 0;
-#endif
+  NEAR_CLOCK_BEGIN();
   static_assert(K <= 64 && NEAR_BUF == 128 && NEAR_BINS == 4 * 64, "register path layout");
   static_assert(K <= MAX_NEAR, "scout record lists");
   constexpr int NW = BLOCK / 64, CH = NEAR_NBK * BLOCK;
@@ -2085,7 +1997,7 @@ __device__ void near_set(const Ctx& C, int t, const double* q, int excl, bool sp
       __syncthreads();
       if (threadIdx.x == 0) { g_L.n_lo = take_c; g_L.n_hi = take_c; }
       __syncthreads();
-      NEAR_COUNT(27);
+      NEAR_COUNT(P_NEAR_DONE);
       continue;
     }
     const double cmin = __longlong_as_double((long long)kmin), cmax = __longlong_as_double((long long)kmax);
@@ -2138,7 +2050,7 @@ __device__ void near_set(const Ctx& C, int t, const double* q, int excl, bool sp
     __syncthreads();
     NEAR_CLOCK(3);
     if (!uni(g_L.nh.fast)) {
-      NEAR_COUNT(26);
+      NEAR_COUNT(P_NEAR_STREAM);
       __syncthreads();
       near_set_stream<K, NN>(C, t, q, excl);
       return;
@@ -2196,7 +2108,7 @@ __device__ void near_set(const Ctx& C, int t, const double* q, int excl, bool sp
     if (threadIdx.x == 0) { g_L.n_lo = take; g_L.n_hi = take; }
     __syncthreads();
     NEAR_CLOCK(5);
-    NEAR_COUNT(27);
+    NEAR_COUNT(P_NEAR_DONE);
   }
   if (threadIdx.x == 0) { g_L.nk = tot_all; g_L.S.near_nodes += n; }
   __syncthreads();
@@ -2571,11 +2483,7 @@ __device__ __forceinline__ void job_header(const Ctx& C, bool need, bool sfv) {
     J.ntiles = (ne * np1 + J.ct - 1) / J.ct;
     J.self = g_L.S.self; J.map = g_L.S.map;
     J.seq = ++g_L.job_seq;
-#ifdef SMP_NO_SKIP
-    J.skip = 0;
-#else
     J.skip = J.ntiles > W;  // more tiles than workers: later rounds skip what earlier ones decided
-#endif
     J.sfv = J.skip && sfv;
   }
 }
@@ -2617,9 +2525,7 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
   }
   for (int t = threadIdx.x; t < nt; t += BLOCK) J.rdone[t] = 0;
   if (threadIdx.x < ne) J.first[threadIdx.x] = np1;
-#ifdef SMP_JOB_PROF
-  if (threadIdx.x == 0) st_agent(&jb->dbg[0], wall_clock64());
-#endif
+  JOBPROF_PUBLISHED(jb);
   PROF_BEGIN();
   if (threadIdx.x == 0) { g_L.S.prof[P_TFK] += _pt - tj0; g_L.S.prof[P_TTEST]++; }  // job publication
   TR();
@@ -2668,9 +2574,9 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
         if (st != 1 && now - t_wait > 200000000ull) {  // 2 s: a job never takes that long -- fail, never hang
           g_L.S.status = -5;
           g_L.S.phase = 2;
-          g_L.S.prof[28] = (unsigned long long)left;
-          g_L.S.prof[29] = (unsigned long long)nt;
-          g_L.S.prof[31] = (unsigned long long)seq;
+          g_L.S.prof[P_JOBTO_LEFT] = (unsigned long long)left;
+          g_L.S.prof[P_JOBTO_TILES] = (unsigned long long)nt;
+          g_L.S.prof[P_JOBTO_SEQ] = (unsigned long long)seq;
           st = 1;
         }
         J.go[k] = st;
@@ -2701,7 +2607,7 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
     __builtin_amdgcn_s_sleep(1);
   }
   TR();
-  if (threadIdx.x == 0) g_L.S.prof[P_TCENTRE] += pclk() - tj1;  // waiting for helpers' tiles
+  if (threadIdx.x == 0) g_L.S.prof[P_TCENTRE] += wall_clock64() - tj1;  // waiting for helpers' tiles
   // first collision per job edge from the tile masks
   for (int t = threadIdx.x; t < nt; t += BLOCK) {
     unsigned m = J.rmask[t];
@@ -2716,7 +2622,7 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
   if (threadIdx.x < ne) g_L.eg_first[J.emap[threadIdx.x]] = J.first[threadIdx.x];
   PROF_END(P_TILES);
   if (threadIdx.x == 0) {
-    g_L.S.prof[pslot] += pclk() - _pt;
+    g_L.S.prof[pslot] += wall_clock64() - _pt;
     g_L.S.prof[P_NTILES] += nt;
     g_L.S.prof[pslot + 8] += J.nslots;
   }
@@ -2733,18 +2639,6 @@ __device__ __forceinline__ void edge_validity_job(const Ctx& C, int E, int pslot
 // each slice's answer is its first strict minimum; the near lists take every entry whose rank over all slices' lists
 // is below SCAN_K (an entry beyond a slice's K-th cannot rank below K: K entries are ahead of it).
 constexpr unsigned SCAN_HDR = 1u | 1u << 18;  // edge-count field 1 (33 payload words), scan job bit
-// SMP_SCAN_PROF builds (tools/scan_probe.py): clocks of the distributed scans, summed over every scan of the leader and
-// the scouts, read by smp_debug_scanprof: [0] scans, [1] write-back + publication, [2] own slice, [3] collection,
-// [4] merge, [5] stolen slices, [6] collection rounds, [7] helper slices, [8] helper pickup (publication -> acquire),
-// [9] helper acquire, [10] helper slice, [11] publication -> helper result stored, [12] near scans, [13] their
-// collection, [14] participants, [15] nodes, [16] near scans' own slice, [17] near merge, [18] near helper slices,
-// [19] their slice clocks
-#ifdef SMP_SCAN_PROF
-__device__ unsigned long long g_scanprof[24];
-#define SCANPROF_ADD(k, v) atomicAdd(&g_scanprof[k], (unsigned long long)(v))
-#else
-#define SCANPROF_ADD(k, v)
-#endif
 constexpr unsigned long long SCAN_WAIT = 2000;  // device-clock ticks (20 us) without progress before stealing a slice
 
 // Slice w of [i0, n) over P participants, in index order, 64-node multiples.  The publisher's slice 0 is a fraction
@@ -2821,9 +2715,7 @@ __device__ __forceinline__ void scan_helper(const Ctx& C, JobLds& J, int worker,
   const double r = __hiloint2double((int)J.words[21], (int)J.words[20]);
   const int w = C.Q.nworkers - worker;
   if (w < 1 || w >= P) return;
-#ifdef SMP_SCAN_PROF
-  const unsigned long long hp0 = wall_clock64();
-#endif
+  SCANPROF_CLOCK(hp0);
   // tree words stored by the leader since this CU last cached them: drop stale copies (consumer form: one acquire,
   // its wait, a barrier, then plain loads)
   if (threadIdx.x < 64) {
@@ -2831,19 +2723,10 @@ __device__ __forceinline__ void scan_helper(const Ctx& C, JobLds& J, int worker,
     drain();
   }
   __syncthreads();
-#ifdef SMP_SCAN_PROF
-  const unsigned long long hp1 = wall_clock64();
-#endif
+  SCANPROF_CLOCK(hp1);
   ScanLds& X = J.scan;
   scan_slice<true>(C, near, t, q, i0, n, excl, r, P, w, X);
-#ifdef SMP_SCAN_PROF
-  if (threadIdx.x == 0) {
-    const unsigned long long hp2 = wall_clock64(), pub = ld_agent(&C.Q.jb->dbg[8]);
-    SCANPROF_ADD(7, 1); SCANPROF_ADD(8, hp0 - pub); SCANPROF_ADD(9, hp1 - hp0); SCANPROF_ADD(10, hp2 - hp1);
-    SCANPROF_ADD(11, hp2 - pub);
-    if (near) { SCANPROF_ADD(18, 1); SCANPROF_ADD(19, hp2 - hp1); }
-  }
-#endif
+  SCANPROF_HELPER(C, near, hp0, hp1);
   unsigned long long* out = C.Q.jb->sres[w];
   if (!near) {
     if (threadIdx.x == 0) {
@@ -2904,9 +2787,7 @@ __device__ void scan_run(const Ctx& C, int near, int t, const double* q, int i0,
   if (threadIdx.x < SCAN_P) { M.done[threadIdx.x] = 0; M.bad[threadIdx.x] = 0; }
   __syncthreads();
   if (threadIdx.x == 0) { g_L.job_seq = seq; M.ndone = 0; }
-#ifdef SMP_SCAN_PROF
-  const unsigned long long sp0 = wall_clock64();
-#endif
+  SCANPROF_CLOCK(sp0);
   // the helpers read the tree through their own CUs and XCDs: the tree stores (this workgroup's, or the leader's on
   // this XCD for a scout) are written back before the job is published (MI355X_MICROARCH.md producer form)
   drain();
@@ -2916,20 +2797,16 @@ __device__ void scan_run(const Ctx& C, int near, int t, const double* q, int i0,
     drain();
   }
   __syncthreads();
-#ifdef SMP_SCAN_PROF
-  const unsigned long long sp1 = wall_clock64();
-  if (threadIdx.x == 0) st_agent(&C.Q.jb->dbg[8], sp1);
-#endif
+  SCANPROF_CLOCK(sp1);
+  SCANPROF_PUBLISHED(C, sp1);
   TR();
   scan_publish(C, seq, near, t, q, i0, n, excl, r, P);
   scan_slice<true>(C, near, t, q, i0, n, excl, r, P, 0, X);
   TR();
   merge_put(M, X, near, 0);
   __syncthreads();
-#ifdef SMP_SCAN_PROF
-  const unsigned long long sp2 = wall_clock64();
-  int sp_rounds = 0, sp_steals = 0;
-#endif
+  SCANPROF_CLOCK(sp2);
+  SCANPROF_COUNTERS(sp_rounds, sp_steals);
   const JobBoard* jb = C.Q.jb;
   unsigned long long t_prog = wall_clock64();
   int last_done = 0;
@@ -3033,9 +2910,7 @@ __device__ void scan_run(const Ctx& C, int near, int t, const double* q, int i0,
     }
     __syncthreads();
     const int go = uni(M.go[k]);
-#ifdef SMP_SCAN_PROF
-    ++sp_rounds;
-#endif
+    SCANPROF_INC(sp_rounds);
     if (go == 1) break;
     TR();
     if (go == 2) {
@@ -3043,24 +2918,14 @@ __device__ void scan_run(const Ctx& C, int near, int t, const double* q, int i0,
       scan_slice<true>(C, near, t, q, i0, n, excl, r, P, w, X);
       merge_put(M, X, near, w);
       if (threadIdx.x == 0) { M.ndone++; t_prog = wall_clock64(); }
-#ifdef SMP_SCAN_PROF
-      ++sp_steals;
-#endif
+      SCANPROF_INC(sp_steals);
       __syncthreads();
       continue;
     }
     __builtin_amdgcn_s_sleep(1);
   }
   __syncthreads();
-#ifdef SMP_SCAN_PROF
-  if (threadIdx.x == 0) {
-    const unsigned long long sp3 = wall_clock64();
-    SCANPROF_ADD(0, 1); SCANPROF_ADD(1, sp1 - sp0); SCANPROF_ADD(2, sp2 - sp1); SCANPROF_ADD(3, sp3 - sp2);
-    SCANPROF_ADD(5, sp_steals); SCANPROF_ADD(6, sp_rounds); SCANPROF_ADD(14, P); SCANPROF_ADD(15, n - i0);
-    if (near) { SCANPROF_ADD(12, 1); SCANPROF_ADD(13, sp3 - sp2); SCANPROF_ADD(16, sp2 - sp1); }
-    g_L.spc_t = sp3;
-  }
-#endif
+  SCANPROF_RUN(near, P, n - i0, sp0, sp1, sp2, sp_steals, sp_rounds);
 }
 
 // The (distance key, id) minimum of the P slices' nearest results (each wave computes it: lane w reads slice w; a serial
@@ -3080,9 +2945,7 @@ __device__ int nearest_dist(const Ctx& C, int t, const double* q, int i0, int n,
   int bi;
   merge_nearest(M, P, bk, bi);
   __syncthreads();
-#ifdef SMP_SCAN_PROF
-  if (threadIdx.x == 0) SCANPROF_ADD(4, wall_clock64() - g_L.spc_t);
-#endif
+  SCANPROF_MERGED();
   *d_out = __longlong_as_double((long long)bk);
   return bi;
 }
@@ -3147,9 +3010,7 @@ __device__ void near_set_dist(const Ctx& C, int t, const double* q, int excl, bo
     if (threadIdx.x == 0) { g_L.fnn_d = __longlong_as_double((long long)bk); g_L.fnn_id = bi; }
   }
   __syncthreads();
-#ifdef SMP_SCAN_PROF
-  if (threadIdx.x == 0) { SCANPROF_ADD(4, wall_clock64() - g_L.spc_t); SCANPROF_ADD(17, wall_clock64() - g_L.spc_t); }
-#endif
+  SCANPROF_NEAR_MERGED();
 }
 
 #ifndef SMP_HELPER_SLEEP
@@ -3266,12 +3127,7 @@ __device__ __noinline__ void helper_main(const Ctx& C, int hidx, JobLds& J) {
       if (hdr & (1u << 19))
         for (int t = threadIdx.x; t < JOB_TILES; t += BLOCK) J.rdone[t] = 0;
     };
-#ifdef SMP_JOB_PROF
-    if (threadIdx.x == 0) for (int i = 0; i < 4; ++i) J.tprof[i] = 0;
-    unsigned long long* tp = J.tprof;
-#else
-    unsigned long long* tp = nullptr;
-#endif
+    JOBPROF_TILE_CLOCKS(J, tp);
     // This helper's first tile (w - 1; never in skip mode, which begins with a worker's second tile) goes straight from
     // the payload when the poll brought all of it (job_tile_mask, `direct`): it waits neither for the decode nor for
     // J.tq at two block barriers.  The decode is left to the helper's second tile of the job, which most jobs do not
@@ -3279,13 +3135,7 @@ __device__ __noinline__ void helper_main(const Ctx& C, int hidx, JobLds& J) {
     const int nt = (ne * (int)((hdr >> 8) & 255) + (1 << ((hdr >> 21) & 3)) - 1) >> ((hdr >> 21) & 3);  // = J.ntiles
     const bool direct = go > 0;
     last = seq;
-#ifdef SMP_JOB_PROF
-    if (threadIdx.x == 0 && w - 1 < nt) {
-      const unsigned long long tpk = ld_agent(&jb->dbg[0]);
-      atomicAdd(&jb->dbg[1], wall_clock64() - tpk);
-      atomicAdd(&jb->dbg[2], 1ull);
-    }
-#endif
+    JOBPROF_PICKUP(jb, w, nt);
     // Every wavefront has read J.seq and J.words[0] above, and wave 0's next poll rewrites both: a block barrier must
     // lie between.  A helper with a tile of this job meets one in the tile; one without (most helpers of a small job:
     // idle, off the job's critical path) takes it here.  Without it a slow wavefront could read the next job's header,
@@ -3304,13 +3154,9 @@ __device__ __noinline__ void helper_main(const Ctx& C, int hidx, JobLds& J) {
       const unsigned m = job_tile_mask(C, K, J, t, tp, seq, dt ? &dj : nullptr, false);
       if (threadIdx.x == 0) st_agent(&jb->res[t], granule(seq, m));
       __syncthreads();
-#ifdef SMP_JOB_PROF
-      if (threadIdx.x == 0) atomicAdd(&jb->dbg[3], wall_clock64() - ld_agent(&jb->dbg[0]));
-#endif
+      JOBPROF_TILE_DONE(jb);
     }
-#ifdef SMP_JOB_PROF
-    if (threadIdx.x == 0 && w - 1 < nt) for (int i = 0; i < 4; ++i) atomicAdd(&jb->dbg[4 + i], J.tprof[i]);
-#endif
+    JOBPROF_TILES_OUT(jb, J, w, nt);
     t_last = wall_clock64();
   }
 }
@@ -3380,9 +3226,7 @@ __device__ bool spec_stage(const Ctx& C, int s, unsigned long long wait) {
     __builtin_amdgcn_s_sleep(1);
   }
   if (threadIdx.x == 0) g_L.S.sc_wait += wall_clock64() - t0;
-#ifdef SMP_WAIT_PROF  // the leader's waits by stage into prof[28..31]: nn / expand, near / choose, rewire, connect
-  if (threadIdx.x == 0) g_L.S.prof[s <= SC_EXPAND ? 28 : s <= SC_CHOOSE ? 29 : s == SC_DONE ? 30 : 31] += wall_clock64() - t0;
-#endif
+  WAIT_CLOCK(s, t0);
   TR();
   if (got < 0) {
     if (threadIdx.x == 0) g_L.sp_on = 0;
@@ -3772,7 +3616,7 @@ __device__ __forceinline__ void edge_validity(const Ctx& C, int E, bool stop_fir
     local_tile(C, nc);
     PROF_END(P_TILES);
     if (threadIdx.x == 0) {
-      g_L.S.prof[pslot] += pclk() - _pt;
+      g_L.S.prof[pslot] += wall_clock64() - _pt;
       g_L.S.prof[P_NTILES]++;
       g_L.S.prof[pslot + 8] += nc;
     }
@@ -3822,10 +3666,7 @@ __device__ void conn_window(const Ctx& C, int t) {
   // nk, n_lo, n_hi, fnn_* and S.n[t]: the rewire stage read its candidates from them before the job (scout_iteration)
   if (threadIdx.x == 0) {
     const bool on = g_L.two_scouts && C.Q.conn_ov_max > 0;
-#ifdef SMP_CONN_PROF
-    g_L.cprof[0] += g_L.two_scouts != 0;
-    g_L.cprof[1] += g_L.two_scouts && (unsigned)(ld_agent(&C.Q.scb->cgo) >> 32) == (unsigned)(g_L.sc_k + 1);
-#endif
+    CONNPROF_WINDOW(C);
     const unsigned long long v = on ? ld_agent(&C.Q.scb->cgo) : 0ull;
     const int nb = (int)(unsigned)v;
     const int go = on && (unsigned)(v >> 32) == (unsigned)(g_L.sc_k + 1) && nb <= C.Q.conn_ov_max;
@@ -4043,12 +3884,7 @@ __device__ __forceinline__ void via_prefix(const double* a, int n, int nv, doubl
 __device__ __noinline__ bool via_costs(const Ctx& C) {
   ViaLds& V = g_L.u.via;
   QState& S = g_L.S;
-#ifdef SMP_VIA_PROF  // thread-0 clocks into prof[29..30]: norms and sums to the barrier, costs and state to the barrier
-  unsigned long long _v0 = threadIdx.x == 0 ? wall_clock64() : 0;
-#define VIA_CLK(k) if (threadIdx.x == 0) { const unsigned long long _v1 = wall_clock64(); S.prof[k] += _v1 - _v0; _v0 = _v1; }
-#else
-#define VIA_CLK(k)
-#endif
+  VIA_CLK_BEGIN();
   const int n = uni(V.n), fin = uni(V.fin), np = uni(S.n_pts);
   const int nv = fin ? n - 1 : n;  // steps that become via nodes
   const int n_via0 = uni(g_L.n_via), nn_t0 = uni(g_L.nn_t), cid0 = uni(g_L.cur.id), cpar0 = uni(g_L.cur.parent);
@@ -4077,7 +3913,7 @@ __device__ __noinline__ bool via_costs(const Ctx& C) {
     }
   }
   __syncthreads();
-  VIA_CLK(29);
+  VIA_CLK(P_VIA_NORMS);
   {  // the nodes' words other than the costs: q = the step's end, e_start, e_target, {id, parent} (stored after the
      // barrier, which would wait for them)
     const int r = threadIdx.x / VIA_WORDS, wd = threadIdx.x - r * VIA_WORDS;
@@ -4141,8 +3977,7 @@ __device__ __noinline__ bool via_costs(const Ctx& C) {
     }
   }
   __syncthreads();
-  VIA_CLK(30);
-#undef VIA_CLK
+  VIA_CLK(P_VIA_COSTS);
   return fin != 0;
 }
 
@@ -4150,14 +3985,10 @@ __device__ void via_chain(const Ctx& C, const double* target) {
   TR();
   PROF_BEGIN();
   for (;;) {
-#ifdef SMP_VIA_PROF  // thread-0 clocks into prof[28] (wave 0's steps, to the barrier) and prof[31] (batches)
-    const unsigned long long _v0 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+    VIA_BATCH_BEGIN();
     if (threadIdx.x < 64) via_steps_w(target);
     __syncthreads();
-#ifdef SMP_VIA_PROF
-    if (threadIdx.x == 0) { g_L.S.prof[28] += wall_clock64() - _v0; g_L.S.prof[31] += 100; }
-#endif
+    VIA_BATCH_STEPPED();
     if (via_costs(C)) break;
   }
   PROF_END(P_VIA);
@@ -4227,32 +4058,14 @@ __device__ void insert_via(const Ctx& C, int t, const ViaNode* rec = nullptr, in
     if (g_L.S.status == -7) g_L.S.phase = 2;
     g_L.n_via = 0;
   }
-  DETAIL_END(_di, 31);
+  DETAIL_END(_di, P_DET_INSVIA);
   __syncthreads();
   TR();
 }
 
-#ifdef SMP_RING_CHECK
-__device__ unsigned long long g_ringchk[64];
-__device__ unsigned long long g_ringdbg[SMP_RING][16];  // sampler: parameters of the slot's sample
-extern "C" void smp_ringchk_dump() {
-  unsigned long long v[64];
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_ringchk), sizeof(v)) == hipSuccess) {
-    double d[64];
-    __builtin_memcpy(d, v, sizeof(d));
-    std::fprintf(stderr, "[smp] ring check: uniform(it) %llu, it-1 %llu, it+1 %llu, other %llu; first mismatch it %llu\n",
-                 v[0], v[1], v[2], v[3], v[4]);
-    std::fprintf(stderr, "[smp]   ring  :");
-    for (int j = 0; j < 8; ++j) std::fprintf(stderr, " %.17g", d[24 + j]);
-    std::fprintf(stderr, "\n[smp]   leader:");
-    for (int j = 0; j < 8; ++j) std::fprintf(stderr, " %.17g", d[32 + j]);
-    std::fprintf(stderr, "\n[smp]   sampler h0 %.17g Crev0 %.17g Crev7 %.17g ctr0 %.17g qmin2 %.17g qmax2 %.17g rev %llx\n",
-                 d[40], d[41], d[42], d[43], d[44], d[45], v[46]);
-    std::fprintf(stderr, "[smp]   leader  h0 %.17g Crev0 %.17g Crev7 %.17g ctr0 %.17g qmin2 %.17g qmax2 %.17g rev %llx\n",
-                 d[48], d[49], d[50], d[51], d[52], d[53], v[54]);
-  }
-}
-#endif
+}  // namespace smp
+#include "smp_plan_ringcheck.h"
+namespace smp {
 // --------------------------------------------------------------------------------------- sampling
 // getRandomConf (control_laws.cpp:1120-1188) draw `inner` of outer attempt `outer` in iteration `it`; the
 // caller keeps the first draw with EE z >= 0.
@@ -4534,56 +4347,7 @@ __device__ __forceinline__ void sample_read(const Ctx& C) {
     if (sample_conf(S, it, g_L.u.smp, g_L.xr) < 0 && threadIdx.x == 0) { S.status = -1; S.phase = 2; }
     __syncthreads();
   }
-#ifdef SMP_RING_CHECK  // debugging: a sample taken from the ring or a record, recomputed here and compared (prof[28..30])
-  else {
-    __shared__ double chk_xr[NJ];
-    __shared__ int chk_bad;
-    sample_conf(S, it, g_L.u.smp, chk_xr);
-    if (threadIdx.x == 0) {
-      int bad = 0;
-      for (int j = 0; j < NJ; ++j) bad |= __double_as_longlong(chk_xr[j]) != __double_as_longlong(g_L.xr[j]);
-      chk_bad = bad;
-      S.prof[30]++;
-      if (bad) { S.prof[28]++; if (!S.prof[29]) S.prof[29] = (unsigned long long)it + 1; }
-      if (bad && g_ringchk[21] == 0) {
-        const RobotDev* rb = (&g_rb);
-        g_ringchk[21] = 1;
-        g_ringchk[4] = (unsigned long long)it;
-        for (int j = 0; j < NJ; ++j) {
-          g_ringchk[24 + j] = (unsigned long long)__double_as_longlong(g_L.xr[j]);
-          g_ringchk[32 + j] = (unsigned long long)__double_as_longlong(chk_xr[j]);
-        }
-        for (int k = 0; k < 7; ++k) g_ringchk[40 + k] = ld_agent(&g_ringdbg[it % SMP_RING][8 + k]);
-        const double lv[6] = {S.h0[1], S.Crev[0], S.Crev[7], S.ctr_rev[0], rb->q_min[2], rb->q_max[2]};
-        for (int k = 0; k < 6; ++k) g_ringchk[48 + k] = (unsigned long long)__double_as_longlong(lv[k]);
-        unsigned long long rv = 0;
-        for (int j = 0; j < NJ; ++j) rv |= (unsigned long long)(rb->rev[j] != 0) << j;
-        g_ringchk[54] = rv;
-      }
-    }
-    __syncthreads();
-    if (uni(chk_bad)) {  // which sample the ring held: prof[20] the uniform one of this iteration, [21] iteration
-      // it - 1's, [22] it + 1's (current parameters), [23] none of them
-      int cls = 23;
-      for (int v = 0; v < 3 && cls == 23; ++v) {
-        if (v == 0) sample_uniform(S, it, g_L.u.smp, chk_xr);
-        else sample_conf(S, v == 1 ? it - 1 : it + 1, g_L.u.smp, chk_xr);
-        if (threadIdx.x == 0) {
-          int same = 1;
-          for (int j = 0; j < NJ; ++j) same &= __double_as_longlong(chk_xr[j]) == __double_as_longlong(g_L.xr[j]);
-          chk_bad = same;
-        }
-        __syncthreads();
-        if (uni(chk_bad)) cls = 20 + v;
-        __syncthreads();
-      }
-      if (threadIdx.x == 0) {
-        g_ringchk[cls - 20]++;
-      }
-      __syncthreads();
-    }
-  }
-#endif
+  else ring_check_sample(S, it);  // (SMP_RING_CHECK builds: the sample taken from the ring or a record, recomputed)
 }
 
 // --------------------------------------------------------------------------------------- tree updates
@@ -4840,7 +4604,7 @@ __device__ void rewire(const Ctx& C, int t) {
         T.first_child[g_L.xn.id] = v;
         DETAIL_BEGIN(_dc);
         cost_update(C, t, v, red);
-        DETAIL_END(_dc, 29);
+        DETAIL_END(_dc, P_DET_COSTUPD);
         S.edges[t]++;
         S.rewires[t]++;
         if (pub) {
@@ -4857,7 +4621,7 @@ __device__ void rewire(const Ctx& C, int t) {
     e0 = uni(g_L.rw_next);
     if (e0 >= cnt) break;
   }
-  DETAIL_END(_dr, 28);
+  DETAIL_END(_dr, P_DET_REWIRE);
   __syncthreads();
   TR();
 }
@@ -5163,7 +4927,7 @@ __device__ void connect_graphs(const Ctx& C, int t, bool crec = false, bool xrow
         if (threadIdx.x == 0) { g_L.tree_expand = 1; g_L.best_nv = g_L.sol[0]; }
         __syncthreads();
       }
-      DETAIL_END(_dn, 30);
+      DETAIL_END(_dn, P_DET_CONNECT);
     }
   }
   insert_via(C, t);
@@ -5218,14 +4982,6 @@ __device__ bool conn_stage(const Ctx& C, int B) {
 // direct edge and via chain (connectGraphs without a solution has no near loop, birrt_star.cpp:2608-2812) -- and the
 // leader only counts and inserts.  Returns false, having changed nothing, if the record does not hold (the caller
 // runs the iteration itself); a record whose connect part does not hold is completed by connect_graphs.
-// Outcome counters of pre_commit in prof[28..31] (committed / no usable record / a newer nearest node / connect
-// completed by connect_graphs); those slots belong to the profiling builds' own clocks otherwise.
-#if defined(SMP_DETAIL_PROF) || defined(SMP_JOB_PROF) || defined(SMP_NEAR_PROF) || defined(SMP_SAMPLE_PROF) || \
-    defined(SMP_VIA_PROF) || defined(SMP_WAIT_PROF)
-#define PRE_COUNT(k)
-#else
-#define PRE_COUNT(k) if (threadIdx.x == 0) g_L.S.prof[28 + (k)]++
-#endif
 // Leader: the pre-solution record of this iteration, complete in g_L.prer -- from sample_read's round, else polled
 // (every granule tagged) until it is or SCOUT_WAIT passes or the scout has left.  All threads.
 __device__ bool pre_wait(const Ctx& C) {
@@ -5269,120 +5025,9 @@ __device__ bool pre_wait(const Ctx& C) {
   return true;
 }
 
-#ifdef SMP_PRE_VERIFY
-// Debugging build: every record-committed decision is recomputed the full way and compared; g_pv[0] counts checks,
-// g_pv[1] holds the first mismatch: iteration | kind << 40 (1 nearest, 2 expand edge, 3 connect nearest, 4 connect
-// edge, 5 x_new / edge costs) | block << 48; read by smp_debug_preverify.
-__device__ unsigned long long g_pv[4];
-__device__ void pv_fail(int kind) {
-  if (threadIdx.x == 0)
-    atomicCAS(&g_pv[1], 0ull, (unsigned long long)g_L.S.iter | ((unsigned long long)kind << 40) |
-                                  ((unsigned long long)blockIdx.x << 48));
-}
-__device__ void pre_verify_expand(const Ctx& C, int A) {
-  const PreRec& P = g_L.prer;
-  double d;
-  int full = nearest_scan(C, A, g_L.xr, 0, &d);
-  full = d < 10000.0 ? full : 0;
-  if (threadIdx.x == 0) atomicAdd(&g_pv[0], 1ull);
-  if (uni(full != (P.nn_d < 10000.0 ? P.nn_id : 0))) pv_fail(1);
-  if (threadIdx.x == 0) {
-    NodeRef nn;
-    load_node(C, A, full, &nn);
-    for (int j = 0; j < NJ; ++j) { g_L.ext[j] = g_L.xr[j]; }
-    step_towards((&g_rb), nn.q, g_L.ext, g_L.S.step);
-    for (int j = 0; j < NJ; ++j) { g_L.eg_start[0][j] = nn.q[j]; g_L.eg_target[0][j] = g_L.ext[j]; }
-    for (int k = 0; k < 3; ++k) g_L.eg_base[0][k] = nn.c[k];
-    g_L.eg_need[0] = 1;
-    g_L.rec_grp = -1;
-  }
-  for (int e = 1 + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
-  __syncthreads();
-  edge_costs(C, 1);
-  edge_validity(C, 1, false, P_XEXPAND);
-  bool bad_costs = false;
-  for (int j = 0; j < NJ; ++j) bad_costs |= g_L.eg_end[0][j] != P.end[j] || g_L.eg_start[0][j] != P.nn_q[j];
-  for (int k = 0; k < 3; ++k) bad_costs |= g_L.eg_cost[0][k] != P.nn_c[k] + P.acc[k];
-  if (uni(g_L.eg_first[0] != P.first)) pv_fail(2);
-  if (uni(bad_costs)) pv_fail(5);
-  __syncthreads();
-}
-__device__ void pre_verify_connect(const Ctx& C, int B, int cid) {
-  const PreRec& P = g_L.prer;
-  double d;
-  int full = nearest_scan(C, B, g_L.xn.q, 0, &d);
-  full = d < 10000.0 ? full : 0;
-  if (uni(full != cid)) pv_fail(3);
-  if (threadIdx.x == 0) {
-    NodeRef xc;
-    load_node(C, B, full, &xc);
-    for (int j = 0; j < NJ; ++j) { g_L.eg_start[0][j] = xc.q[j]; g_L.eg_target[0][j] = g_L.xn.q[j]; }
-    for (int k = 0; k < 3; ++k) g_L.eg_base[0][k] = xc.c[k];
-    g_L.eg_need[0] = 1;
-    g_L.rec_grp = -1;
-  }
-  for (int e = 1 + threadIdx.x; e < MAXE; e += BLOCK) g_L.eg_need[e] = 0;
-  __syncthreads();
-  edge_costs(C, 1);
-  edge_validity(C, 1, false, P_XCONNECT);
-  if (uni(P.pre_ok && P.need && g_L.eg_first[0] != P.cn_first)) pv_fail(4);
-  __syncthreads();
-  if (!uni(P.pre_ok)) return;
-  // the connect outcome the full path would take (connect_graphs without a solution): flag, via chain, last node
-  if (threadIdx.x == 0) {
-    QState& S = g_L.S;
-    double sol[3];
-    for (int k = 0; k < 3; ++k) sol[k] = g_L.eg_cost[0][k] + g_L.xn.c[k];
-    const int need = sol[0] < S.cbest[0];
-    int flag = 0;
-    if (need) {
-      const int f = g_L.eg_first[0];
-      if (f > S.n_pts) flag = 1;
-      else {
-        const int lv = f == 0 ? 0 : f - 1;
-        if (lv != 0) { for (int j = 0; j < NJ; ++j) g_L.ext[j] = g_L.eg_start[0][j] + lv * g_L.eg_step[0][j]; flag = 2; }
-      }
-    }
-    bool bad = need != P.need || flag != P.flag;
-    for (int k = 0; k < 3; ++k) bad |= sol[k] != P.sol[k];
-    if (bad) pv_fail(8);
-    g_L.flag = flag;
-    g_L.n_via = 0;
-    g_L.nn_t = S.n[B];
-    load_node(C, B, cid, &g_L.cur);
-  }
-  __syncthreads();
-  const int flag = uni(g_L.flag);
-  if (!flag) return;
-  via_chain(C, flag == 1 ? g_L.xn.q : g_L.ext);
-  if (threadIdx.x == 0) {
-    const int par = (int)(g_L.S.iter & (SCOUT_SLOTS - 1));
-    const ScoutBoard* sb = C.Q.scbs[g_L.asked[par] - 1];
-    const int off = g_L.S.n[B] - P.XB;
-    bool bad = g_L.n_via != P.nv;
-    for (int k = 0; k < g_L.n_via && k < P.nv && !bad; ++k) {
-      const ViaNode& a = C.Q.via[k];
-      const ViaNode& b = sb->pre_via[par][k];
-      for (int j = 0; j < NJ; ++j)
-        bad |= a.q[j] != __longlong_as_double((long long)ld_agent((const unsigned long long*)&b.q[j])) ||
-               a.e_start[j] != __longlong_as_double((long long)ld_agent((const unsigned long long*)&b.e_start[j])) ||
-               a.e_target[j] != __longlong_as_double((long long)ld_agent((const unsigned long long*)&b.e_target[j]));
-      for (int c = 0; c < 3; ++c) bad |= a.c[c] != __longlong_as_double((long long)ld_agent((const unsigned long long*)&b.c[c]));
-      const int bid = ld_agent(&b.id), bpar = ld_agent(&b.parent);
-      bad |= a.id != (bid >= P.XB ? bid + off : bid) || a.parent != (bpar >= P.XB ? bpar + off : bpar);
-    }
-    if (bad) pv_fail(6);
-    bool bs = false;
-    for (int j = 0; j < NJ; ++j) bs |= g_L.sel.q[j] != P.sel_q[j] || g_L.sel_start[j] != P.sel_start[j] || g_L.sel_target[j] != P.sel_target[j];
-    for (int k = 0; k < 3; ++k) bs |= g_L.sel.c[k] != P.sel_c[k];
-    bs |= g_L.sel.id != (P.sel_id >= P.XB ? P.sel_id + off : P.sel_id);
-    bs |= g_L.sel.parent != (P.sel_parent >= P.XB ? P.sel_parent + off : P.sel_parent);
-    if (bs) pv_fail(7);
-    g_L.n_via = 0;
-  }
-  __syncthreads();
-}
-#endif
+}  // namespace smp
+#include "smp_plan_preverify.h"
+namespace smp {
 
 __device__ __forceinline__ bool pre_commit(const Ctx& C, int A, int B) {
   if (!uni(g_L.sp_on) || !pre_wait(C)) { PRE_COUNT(1); return false; }
@@ -5397,9 +5042,7 @@ __device__ __forceinline__ bool pre_commit(const Ctx& C, int A, int B) {
   }
   PRE_COUNT(0);
   TR();
-#ifdef SMP_PRE_VERIFY
-  pre_verify_expand(C, A);
-#endif
+  PRE_VERIFY_EXPAND(C, A);
   if (threadIdx.x == 0) {
     QState& S = g_L.S;
     S.nn_nodes += nA;
@@ -5437,9 +5080,7 @@ __device__ __forceinline__ bool pre_commit(const Ctx& C, int A, int B) {
     cid = nearest(C, B, g_L.xn.q);
   }
   TR();
-#ifdef SMP_PRE_VERIFY
-  if (rec) pre_verify_connect(C, B, cid);
-#endif
+  PRE_VERIFY_CONNECT(rec, C, B, cid);
   if (!rec || !uni(P.pre_ok) || C.Q.pre_commit == 2) {
     PRE_COUNT(3);
     if (threadIdx.x == 0) load_node(C, B, cid, &g_L.xc);
@@ -5489,12 +5130,10 @@ __device__ __forceinline__ bool pre_commit(const Ctx& C, int A, int B) {
 // iterations (tools/experiments/README.md), builds that inline it run clean.
 __device__ __forceinline__ void iteration(const Ctx& C) {
   const int A = uni(g_L.S.A), B = 1 - A;
-  unsigned long long _t0 = threadIdx.x == 0 ? pclk() : 0, _t1;
-#ifdef SMP_TRACE
-  if (threadIdx.x == 0) { g_L.tit = g_L.S.iter; g_L.tbar = 0; }
-#endif
+  unsigned long long _t0 = threadIdx.x == 0 ? wall_clock64() : 0, _t1;
+  TR_ITERATION();
   TR();
-#define PHASE(k) if (threadIdx.x == 0) { _t1 = pclk(); g_L.S.prof[k] += _t1 - _t0; _t0 = _t1; }
+#define PHASE(k) if (threadIdx.x == 0) { _t1 = wall_clock64(); g_L.S.prof[k] += _t1 - _t0; _t0 = _t1; }
   // two waves in parallel (disjoint LDS fields; each a serial chain of LDS reads)
   if (threadIdx.x == 0) sample_version(C);
   else if (threadIdx.x == 64 && C.Q.nscouts > 0) scout_slots();
@@ -5673,16 +5312,16 @@ __device__ __forceinline__ void iteration(const Ctx& C) {
 // Scout: publishes `nbytes` of section p of its record, then (stage >= 0) the stage granule once every wave's
 // stores are drained.
 __device__ void sc_publish(const Ctx& C, int par, unsigned tag, int stage) {
-  const unsigned long long t0 = threadIdx.x == 0 ? pclk() : 0;
+  const unsigned long long t0 = threadIdx.x == 0 ? wall_clock64() : 0;
   drain();
   __syncthreads();
   if (threadIdx.x == 0) {
     st_agent(&C.Q.scb->stage[par], granule(tag, (unsigned)stage | (g_L.sc_mod & 0xfffu) << 8));
-    g_L.S.prof[29] += pclk() - t0;
+    g_L.S.prof[P_SC_PUBLISH] += wall_clock64() - t0;
   }
   __syncthreads();
 }
-#define SC_PHASE(k) if (threadIdx.x == 0) { const unsigned long long _t = pclk(); g_L.S.prof[k] += _t - _ts; _ts = _t; }
+#define SC_PHASE(k) if (threadIdx.x == 0) { const unsigned long long _t = wall_clock64(); g_L.S.prof[k] += _t - _ts; _ts = _t; }
 // True (block-uniform) once the leader has moved past the iteration with record tag `tag` (iteration tag - 1):
 // the rest of the record would not be used.
 __device__ bool sc_stale(const Ctx& C, unsigned tag) {
@@ -5718,9 +5357,7 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
   const int tb = 1 - t;
   // (the rewire job's window has seen cgo and run the scan, conn_window: straight to the rows)
   const bool scanned = uni(g_L.conn_ov) != 0;
-#ifdef SMP_CONN_PROF
-  const unsigned long long _c0 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+  CONNPROF_CLOCK(_c0);
   for (int k = 0; !scanned; k ^= 1) {
     if (threadIdx.x == 0) {
       const unsigned long long v = ld_agent(&sb->cgo);
@@ -5738,9 +5375,7 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
     if (go > 0) break;
     __builtin_amdgcn_s_sleep(2);
   }
-#ifdef SMP_CONN_PROF
-  const unsigned long long _c1 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+  CONNPROF_CLOCK(_c1);
   if (!scanned) {
     // the tree's stores are the leader's (drained before cgo): drop stale cached copies
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -5749,9 +5384,7 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
     // the near set of x_new and its nearest node (no exclusion) in one pass over tree_B
     [[clang::always_inline]] near_set<20, true>(C, tb, g_L.xn.q, g_L.xn.id);
   }
-#ifdef SMP_CONN_PROF
-  const unsigned long long _c2 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+  CONNPROF_CLOCK(_c2);
   if (threadIdx.x == 0) {
     double d = g_L.fnn_d;
     int cid = g_L.fnn_id;
@@ -5816,12 +5449,7 @@ __device__ void scout_connect(const Ctx& C, long long it, int t, int par, unsign
   __syncthreads();
   sc_copy_out(sb, par, &R.cc, sizeof(ScoutConn));
   sc_publish(C, par, tag, SC_CONN);
-#ifdef SMP_CONN_PROF
-  if (threadIdx.x == 0) {
-    g_L.cprof[4]++;
-    g_L.cprof[5] += (unsigned)(wall_clock64() - _c0); g_L.cprof[6] += (unsigned)(_c1 - _c0); g_L.cprof[7] += (unsigned)(_c2 - _c1);
-  }
-#endif
+  CONNPROF_CONNECT(_c0, _c1, _c2);
 }
 
 // Scout: ends a record without connect's scans; a post-solution record of two scouts still reaches stage SC_CONN
@@ -5975,7 +5603,7 @@ __device__ __forceinline__ bool pre_newer(const Ctx& C, int t, int X, int XB) {
   if (threadIdx.x == 0) {
     S.n[t] = Xn;
     S.n[1 - t] = XBn;
-    S.prof[26]++;
+    S.prof[P_SC_REDONE]++;
     R.cn.ok = 0;
     R.pre.ok = 0;
     R.nn.ok = 0; R.ex.ok = 0; R.nr.ok = 0; R.n_choose = 0; R.n_rewire = 0; R.cc.ok = 0; R.cc.nfirst = -1;
@@ -5996,13 +5624,11 @@ __device__ void scout_iteration(const Ctx& C, long long it, int t, int X, int op
   const int par = (int)(it & (SCOUT_SLOTS - 1));
   const unsigned tag = (unsigned)(it + 1);
   (void)jb;
-  unsigned long long _ts = threadIdx.x == 0 ? pclk() : 0;
-#ifdef SMP_TRACE
-  if (threadIdx.x == 0) g_L.tit = it;
-#endif
+  unsigned long long _ts = threadIdx.x == 0 ? wall_clock64() : 0;
+  TR_PASS(it);
   TR();
   if (threadIdx.x == 0) {
-    S.prof[30]++;
+    S.prof[P_SC_PASSES]++;
     S.n[t] = X;
     S.n[1 - t] = XB;
     R.cn.ok = 0;
@@ -6127,14 +5753,10 @@ redo:
     [[clang::always_inline]] edge_validity(C, 2, false, P_XEXPAND, OV_NONE, t);
   } else {
     // (post-solution: R.ex and the edge's start, target and sums go out under the job, sc_early_send)
-#ifdef SMP_CONN_PROF
-    const unsigned long long _e0 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+    CONNPROF_CLOCK(_e0);
     [[clang::always_inline]] edge_validity(C, 1, false, P_XEXPAND, opt ? OV_NEAR_EXPAND : OV_NONE, t, -1,
                                            opt ? EARLY_EXPAND : EARLY_NONE, par);
-#ifdef SMP_CONN_PROF
-    if (threadIdx.x == 0 && opt) { g_L.cprof[10] += (unsigned)(wall_clock64() - _e0); g_L.cprof[11]++; }
-#endif
+    CONNPROF_EXPAND(_e0, opt);
   }
   if (opt) sc_first_send(C, EARLY_EXPAND, par, 1);
   if (threadIdx.x == 0) {
@@ -6221,13 +5843,9 @@ redo:
   if (sc_moved(C)) return;
   // near set of x_new (the leader's, before choose_parent)
   if (!(uni(g_L.ext_nn) && take_spec(OV_NEAR_EXPAND))) {
-#ifdef SMP_CONN_PROF
-    const unsigned long long _n0 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+    CONNPROF_CLOCK(_n0);
     [[clang::always_inline]] near_set<20>(C, t, g_L.xn.q, X);
-#ifdef SMP_CONN_PROF
-    if (threadIdx.x == 0) { g_L.cprof[2]++; g_L.cprof[3] += (unsigned)(wall_clock64() - _n0); }
-#endif
+    CONNPROF_NEAR2(_n0);
   }
   if (threadIdx.x < 20) {
     R.nr.lo_i[threadIdx.x] = g_L.lo_i[threadIdx.x]; R.nr.lo_c[threadIdx.x] = g_L.lo_c[threadIdx.x];
@@ -6263,8 +5881,10 @@ redo:
     // wave 1: the hi list's rows for the rewire stage, final with the near set (a node's configuration never changes;
     // its cost and parent only steer which edges the scout checks, and the leader takes a result by the edge's bits)
     const TreeDev& T = C.Q.tr[t];
-    const int i = (int)threadIdx.x - 64, v = g_L.hi_i[i], cap = g_L.S.cap;
-    BCHK(v, cap, __LINE__, t);
+    const int i = (int)threadIdx.x - 64;
+    int v = g_L.hi_i[i];  // (not const: an SMP_BOUNDS build replaces an id out of range)
+    const int cap = g_L.S.cap;
+    BCHK(v, cap, SMP_SITE, t);
     double q[NJ];
     for (int j = 0; j < NJ; ++j) q[j] = T.q[(size_t)j * cap + v];
     const double c0 = T.cost[v];
@@ -6358,13 +5978,9 @@ redo:
     // connect's scan of tree_B under the job (conn_window) when the leader has reported the tree final by
     // then.  It writes nk, n_lo, n_hi, lo_*, hi_*, fnn_* and S.n[1 - t]: this stage read hi_i, nk, n_hi and sc_h* above,
     // before the job; after it only eg_need / eg_first are read (sc_first_send), and scout_connect reads the scan
-#ifdef SMP_CONN_PROF
-    const unsigned long long _r0 = threadIdx.x == 0 ? wall_clock64() : 0;
-#endif
+    CONNPROF_CLOCK(_r0);
     [[clang::always_inline]] edge_validity(C, cnt, false, P_XREWIRE, OV_NONE, 1 - t, -1, EARLY_REWIRE, par, true);
-#ifdef SMP_CONN_PROF
-    if (threadIdx.x == 0) { g_L.cprof[8] += (unsigned)(wall_clock64() - _r0); g_L.cprof[9]++; }
-#endif
+    CONNPROF_REWIRE(_r0);
     sc_first_send(C, EARLY_REWIRE, par, cnt);
   } else {
     sc_copy_out(sb, par, &R.n_choose, 4 * sizeof(int));
@@ -6411,9 +6027,7 @@ __device__ __noinline__ void scout_main(Ctx& C, int which) {
     g_L.job_seq = 0;
     g_L.in_job = 0;
     g_L.ov_local = 0; g_L.conn_ov = 0; g_L.conn_ov_n = 0;
-#ifdef SMP_CONN_PROF
-    for (int k = 0; k < 12; ++k) g_L.cprof[k] = 0;
-#endif
+    CONNPROF_RESET();
     g_L.n_via = 0;
     g_L.near_blo = ~0ull;
     g_L.near_bhi = 0;
@@ -6422,22 +6036,14 @@ __device__ __noinline__ void scout_main(Ctx& C, int which) {
     st_agent(&C.Q.scb->xcc, xcc_id() + 1);
     g_L.two_scouts = C.Q.nscouts >= 2;
     g_L.rec_grp = -1;
-#ifdef SMP_TRACE
-    g_L.trole = which + 1 < 3 ? which + 1 : 3;
-    g_L.tit = -1;
-    g_L.tn = g_tlog_n[g_L.trole];
-#endif
+    TR_ROLE(which + 1 < 3 ? which + 1 : 3, -1, g_L.trole);
   }
   __syncthreads();
   unsigned last = 0;
   unsigned long long t_last = wall_clock64();
   // scouts 2 and up only serve iterations before the first solution (scout_ask): in a launch that starts after it
   // they retire at once, with their helpers, instead of polling beside the leader for the whole launch
-#ifdef SMP_NO_RETIRE
-  const bool retired = false;
-#else
   const bool retired = which >= 2 && uni(g_L.S.tree_opt && g_L.S.have_sol);
-#endif
   // the last pass's request: a post-solution pass is rebuilt when the leader rewires its tree after asking for it
   // (early asks, ScoutBoard::rwb / rwe) and the leader has not yet moved past the iteration
   unsigned l_w0 = 0, l_ver = 0;
@@ -6518,7 +6124,7 @@ __device__ __noinline__ void scout_main(Ctx& C, int which) {
     }
     l_w0 = w0; l_ver = ver; l_X = X; l_XB = XB;
     const unsigned long long tb = wall_clock64();
-    if (threadIdx.x == 0) g_L.S.prof[28] += tb - t_last;  // idle: waiting for a request
+    if (threadIdx.x == 0) g_L.S.prof[P_SC_IDLE] += tb - t_last;  // idle: waiting for a request
     for (;;) {  // the pass, rebuilt while the leader rewires its tree under it
       if (opt && C.Q.early_ask) {
         // the tree as the leader left it: a begun rewire commit is waited for until its words are stored
@@ -6554,15 +6160,13 @@ __device__ __noinline__ void scout_main(Ctx& C, int which) {
     }
     last = tag;
     t_last = wall_clock64();
-    if (threadIdx.x == 0) g_L.S.prof[31] += t_last - tb;
+    if (threadIdx.x == 0) g_L.S.prof[P_SC_BUSY] += t_last - tb;
   }
   if (threadIdx.x == 0) {
     st_agent(&C.Q.jb->stop, 1);
     for (int k = 0; k < 32; ++k) st_agent(&C.Q.scb->prof[k], g_L.S.prof[k]);
     st_agent(&C.Q.scb->conn_ov_n, (unsigned long long)g_L.conn_ov_n);
-#ifdef SMP_CONN_PROF
-    for (int k = 0; k < 6; ++k) st_agent(&C.Q.scb->cprof[k], (unsigned long long)g_L.cprof[2 * k] | (unsigned long long)g_L.cprof[2 * k + 1] << 32);
-#endif
+    CONNPROF_STORE(C);
   }
 }
 
@@ -6610,21 +6214,7 @@ __device__ __forceinline__ void sampler_body(const Ctx& C, SamplerLds& L) {
     }
     const long long it = L.next;
     const int st = sample_conf(L.S, (uint32_t)it, L.W, L.out);
-#ifdef SMP_RING_CHECK
-    if (threadIdx.x == 0) {
-      unsigned long long* d = g_ringdbg[it % SMP_RING];
-      st_agent(&d[0], (unsigned long long)it); st_agent(&d[1], (unsigned long long)L.ver);
-      st_agent(&d[2], (unsigned long long)L.S.have_sol);
-      for (int k = 0; k < 3; ++k) st_agent(&d[3 + k], (unsigned long long)__double_as_longlong(L.S.cbest[k]));
-      st_agent(&d[6], (unsigned long long)L.S.informed);
-      const RobotDev* rb = (&g_rb);
-      const double lv[6] = {L.S.h0[1], L.S.Crev[0], L.S.Crev[7], L.S.ctr_rev[0], rb->q_min[2], rb->q_max[2]};
-      for (int k = 0; k < 6; ++k) st_agent(&d[8 + k], (unsigned long long)__double_as_longlong(lv[k]));
-      unsigned long long rv = 0;
-      for (int j = 0; j < NJ; ++j) rv |= (unsigned long long)(rb->rev[j] != 0) << j;
-      st_agent(&d[14], rv);
-    }
-#endif
+    ring_check_params(L, it);  // (SMP_RING_CHECK builds)
     if (st == 0 && threadIdx.x < RING_G) {
       unsigned w;
       if (threadIdx.x < 2 * NJ) {
@@ -6739,11 +6329,7 @@ __global__ void __launch_bounds__(BLOCK) plan_kernel(const RobotDev* __restrict_
         st_agent(reinterpret_cast<int*>(&C.Q.scbs[s]->rwe[t]), g_L.S.rewires[t]);
       }
     drain();  // before any request reaches a scout
-#ifdef SMP_TRACE
-    g_L.trole = 0;
-    g_L.tit = 0;  // the pre-loop's records go with iteration 0's
-    g_L.tn = g_tlog_n[0];
-#endif
+    TR_ROLE(0, 0, 0);  // the pre-loop's records go with iteration 0's
   }
   __syncthreads();
   TR();
@@ -6830,14 +6416,7 @@ __global__ void __launch_bounds__(BLOCK) plan_kernel(const RobotDev* __restrict_
     if (C.Q.lquota > 0 && (g_L.S.phase == 2 || g_L.S.status != 0))
       __hip_atomic_fetch_add(C.Q.lfin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (g_L.S.phase == 2 && g_L.S.t_end == 0) g_L.S.t_end = wall_clock64();
-#ifdef SMP_JOB_PROF
-    if (C.Q.jb) {
-      g_L.S.prof[28] += ld_agent(&C.Q.jb->dbg[1]);
-      g_L.S.prof[29] += ld_agent(&C.Q.jb->dbg[2]);
-      g_L.S.prof[30] += ld_agent(&C.Q.jb->dbg[3]);
-      for (int i = 0; i < 4; ++i) g_L.S.prof[P_TFK + i] += ld_agent(&C.Q.jb->dbg[4 + i]);  // helper tile stages
-    }
-#endif
+    JOBPROF_COLLECT(C);
     *C.Q.st = g_L.S;
     if (C.Q.jb) st_agent(&C.Q.jb->stop, 1);
     for (int s = 0; s < C.Q.nscouts; ++s) st_agent(&C.Q.scbs[s]->stop, 1);
@@ -6947,8 +6526,8 @@ __device__ __forceinline__ void near_probe_body(const double* tqv, const double*
     unsigned long long t1 = wall_clock64();
     for (int rep = 0; rep < reps; ++rep) {
       if constexpr (INL) {
-        if (mode == 4) slice_near_inl<false, true>(tq, tc, cap, 0, n, g_L.xr, excl[k], r, g_L.sc.s, tqf, &g_L.S.prof[20]);
-        else slice_near_inl<true, true>(tq, tc, cap, 0, n, g_L.xr, excl[k], r, g_L.sc.s, tqf, &g_L.S.prof[20]);
+        if (mode == 4) slice_near_inl<false, true>(tq, tc, cap, 0, n, g_L.xr, excl[k], r, g_L.sc.s, tqf, &g_L.S.prof[P_PROBE]);
+        else slice_near_inl<true, true>(tq, tc, cap, 0, n, g_L.xr, excl[k], r, g_L.sc.s, tqf, &g_L.S.prof[P_PROBE]);
       } else {
         if (mode == 1) slice_near<false>(tq, tc, cap, 0, n, g_L.xr, excl[k], r, g_L.sc.s);
         else if (mode == 3) slice_near<true>(tq, tc, cap, 0, n, g_L.xr, excl[k], r, g_L.sc.s);
@@ -6980,7 +6559,7 @@ __device__ __forceinline__ void near_probe_body(const double* tqv, const double*
   if (threadIdx.x == 0) {
     ticks[0] = t_nn;
     ticks[1] = t_near;
-    for (int k = 0; k < 10; ++k) ticks[2 + k] = g_L.S.prof[20 + k];
+    for (int k = 0; k < 10; ++k) ticks[2 + k] = g_L.S.prof[P_PROBE + k];
     // shader clock over the whole probe: s_memtime (shader cycles) and wall-clock ticks
     ticks[12] = __builtin_amdgcn_s_memtime() - m0;
     ticks[13] = wall_clock64() - w0;

@@ -1,4 +1,5 @@
-// Device-resident BiRRT* planner state (one workgroup per query).  Shared by smp_kernels.hip and the host.
+// Device-resident BiRRT* planner state (one workgroup per query).  Shared by smp_kernels.hip (with
+// smp_plan_prof.h, smp_plan_ringcheck.h and smp_plan_preverify.h for everything that measures or checks) and the host.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -49,7 +50,7 @@ struct QState {                // per query, persisted in global memory across l
   long long sc_nn, sc_near, sc_edge_hit, sc_edge_miss;  // scout results used: nearest, near sets, edges (+ misses)
   long long sc_conn_row, sc_conn_batch;  // connects whose nearest node's row / whose candidate batch came from the record
   unsigned long long sc_wait;      // device-clock ticks the leader waited for the scout
-  unsigned long long prof[32];     // device-clock ticks per planner phase (SMP_PROF_* in smp_kernels.hip)
+  unsigned long long prof[32];     // device-clock ticks and counts by slot (P_* and the owner table in smp_plan_prof.h)
   unsigned long long t0, t_first, t_end, deadline;  // device wall clock (0 deadline = none)
   unsigned long long budget_ticks;  // seconds budget in device-clock ticks (has_deadline): deadline = t0 + this
   int has_deadline;

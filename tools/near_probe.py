@@ -34,7 +34,7 @@ for n in (len(conf) // 4, len(conf) // 2, len(conf)):
     print("n %6d  nearest %.2f us  near_set %.2f us per call  (mean k %.0f)" % (
         n, r["t_nearest"] / calls * 1e6, r["t_near"] / calls * 1e6, r["k"].mean()), flush=True)
     pf = r["prof"]
-    if pf[6] + pf[7] > 0:  # SMP_NEAR_PROF build
+    if pf[6] + pf[7] > 0:  # SMP_NEAR_PROF build; pf = slots 20.. of csrc/smp_plan_prof.h's table
         fast = max(pf[7], 1)
         print("         register path %d / fallback %d; steps (us/call): scan %s" % (
             pf[7], pf[6], " ".join("%.2f" % (pf[k] / r["clock_hz"] / fast * 1e6) for k in range(5))), flush=True)

@@ -44,7 +44,7 @@ for iters in [int(v) for v in (sys.argv[1:] or ["2000", "10000", "50000"])]:
         print("   scout (us per pass, %d passes): sample %.1f nn %.1f expand %.1f near %.1f choose %.1f via %.1f rewire %.1f"
               " | publish %.1f busy %.1f idle %.1f | edge_costs %.1f tiles(job) %.1f" % (
                   ns, *[sp[k] * 1e6 / ns for k in (0, 1, 2, 3, 4, 5, 6, 29, 31, 28, 9, 7)]), flush=True)
-    raw = r["phase_raw"]
+    raw = r["phase_raw"]  # QState::prof by slot number: names and owners in csrc/smp_plan_prof.h (the table there)
     if r["first_solution_iter"] < 0 or r["first_solution_iter"] > 0:
         # the leader's pre_commit outcomes (plain builds: prof[28..31]): record committed / no usable record / a node
         # appended since the record's snapshot is nearer / connect redone in full
@@ -55,10 +55,6 @@ for iters in [int(v) for v in (sys.argv[1:] or ["2000", "10000", "50000"])]:
     nj = max(raw[15] * 1e8, 1)
     print("   jobs %d: publish %.1f us, own %.1f us, wait %.1f us per job" % (
         raw[15] * 1e8, raw[12] * 1e6 / nj, raw[13] * 1e6 / nj, raw[14] * 1e6 / nj), flush=True)
-    if os.environ.get("SMP_SAMPLE_PROF"):  # SMP_SAMPLE_PROF build: ellipse sampler stage clocks (ticks, slots 28-30)
-        rounds = max(raw[30], 1)
-        print("   sample_ellipse: %d rounds, stage 1 %.2f us, stage 2 %.2f us per round" % (
-            rounds, raw[28] / 1e2 / rounds, raw[29] / 1e2 / rounds), flush=True)
     if os.environ.get("SMP_JOB_PROF"):  # SMP_JOB_PROF build: helper pickup / tile-finish delay after publication
         n = max(raw[29], 1)
         print("   helpers: %d pickups, pickup %.2f us, tile finished %.2f us after publication (mean)" % (

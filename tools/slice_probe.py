@@ -32,7 +32,7 @@ for n in [int(v) for v in (sys.argv[1:] or ["1024", "2048", "4096", "8192", "163
               c["t_nearest"] / calls * 1e6, a["t_near"] / calls * 1e6, b["t_near"] / calls * 1e6,
               c["t_near"] / calls * 1e6, same), flush=True)
     pf = a["prof"]
-    if pf[6] + pf[7] > 0:  # SMP_NEAR_PROF build: near_set's barrier-separated steps (register path)
+    if pf[6] + pf[7] > 0:  # SMP_NEAR_PROF build: near_set's barrier-separated steps (register path); pf = slots 20.. of csrc/smp_plan_prof.h's table
         fast = max(pf[7], 1)
         print("         near_set register path %d / fallback %d; steps (us/call): %s" % (
             pf[7], pf[6], " ".join("%.2f" % (pf[k] / a["clock_hz"] / fast * 1e6) for k in range(5))), flush=True)

@@ -1,6 +1,7 @@
-"""Device timeline of the planner (SMP_TRACE build): thread 0 of the leader and of the scouts log (source line,
+"""Device timeline of the planner (SMP_TRACE build): thread 0 of the leader and of the scouts log (source site,
 device clock) records for a window of iterations of the C2 query; this prints, per role, the mean time between
-consecutive trace points (keyed by the two source lines) and the raw timeline of two iterations.
+consecutive trace points (keyed by the two sites, file:line of smp_kernels.hip and the smp_plan_*.h headers it includes) and the raw
+timeline of two iterations.
 
   make -C squirrel_motion_planner_amd EXTRA=-DSMP_TRACE BUILD=build_trace OUT=lib/libsmp_gpu_trace.so
   SMP_LIB=squirrel_motion_planner_amd/lib/libsmp_gpu_trace.so python tools/trace_probe.py [iterations]
@@ -9,6 +10,7 @@ import collections
 import ctypes
 import math
 import os
+import re
 import sys
 
 import numpy as np
@@ -39,16 +41,31 @@ a = np.ctypeslib.as_array(buf).astype(np.uint64)
 a = a[a != 0]
 role = (a >> np.uint64(62)).astype(int)
 it = ((a >> np.uint64(54)) & np.uint64(0xff)).astype(int)
-line = ((a >> np.uint64(40)) & np.uint64(0x3fff)).astype(int)
-clk = (a & np.uint64(0xffffffffff)).astype(np.int64)
+# a record (csrc/smp_plan_prof.h TR_RECORD): role << 62 | iteration << 54 | site << 36 | clock; a site (csrc/smp_kernels.h):
+# file << SITE_LINE_BITS | line, the file's number being its place in SITE_FILES there
+CLOCK_BITS, LINE_BITS, FILE_BITS = 36, 13, 5
+line = ((a >> np.uint64(CLOCK_BITS)) & np.uint64((1 << (LINE_BITS + FILE_BITS)) - 1)).astype(int)  # the site word
+clk = (a & np.uint64((1 << CLOCK_BITS) - 1)).astype(np.int64)
+if len(clk):  # the clock field wraps every 2^36 ticks (11 minutes): times relative to the first record
+    clk = ((clk - clk[0] + (1 << (CLOCK_BITS - 1))) % (1 << CLOCK_BITS)) - (1 << (CLOCK_BITS - 1))
 TICK_US = 0.01  # wall clock 100 MHz
-TR_BAR0 = 16000  # smp_kernels.hip TR_BARRIERS: line field = TR_BAR0 + barriers of the leader's iteration
-src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "squirrel_motion_planner_amd",
-                        "csrc", "smp_kernels.hip")).read().split("\n")
+TR_BAR0 = ((1 << FILE_BITS) - 1) << LINE_BITS  # TR_BARRIERS: file SITE_FILE_BARRIERS, line field = barriers of the iteration
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "squirrel_motion_planner_amd", "csrc")
+table = re.search(r"SITE_FILES\[\] = \{(.*?)\};", open(os.path.join(CSRC, "smp_kernels.h")).read(), re.S).group(1)
+files = {k: (name, open(os.path.join(CSRC, name)).read().split("\n"))  # file number -> (file name, its lines)
+         for k, name in enumerate(re.findall(r'"([^"]+)"', table))}
 
 
-def func_of(ln):
-    for k in range(ln - 1, -1, -1):
+def site_of(w):
+    """file:line of a site word."""
+    f, ln = w >> LINE_BITS, w & ((1 << LINE_BITS) - 1)
+    return "%s:%d" % (files[f][0].replace("smp_plan_", "").replace("smp_", ""), ln) if f in files else "?%d:%d" % (f, ln)
+
+
+def func_of(w):
+    f, ln = w >> LINE_BITS, w & ((1 << LINE_BITS) - 1)
+    src = files[f][1] if f in files else []
+    for k in range(min(ln, len(src)) - 1, -1, -1):
         t = src[k]
         if t.startswith("__device__") or t.startswith("__global__"):
             name = t.split("(")[0].split()[-1]
@@ -80,8 +97,8 @@ for rl in sorted(set(role.tolist())):
         rl, "leader" if rl == 0 else "scout %d" % rl, len(its), tot / max(len(its) - 1, 1)))
     rows = sorted(trans.items(), key=lambda kv: -kv[1][0])
     for (l0, l1), (s, c) in rows[:int(os.environ.get("SMP_TRACE_ROWS", "40"))]:
-        print("  %5.2f us/iter  %6.2f us x %4d   %4d %-22s -> %4d %-22s" % (
-            s / max(len(its), 1), s / c, c, l0, func_of(l0)[:22], l1, func_of(l1)[:22]))
+        print("  %5.2f us/iter  %6.2f us x %4d   %18s %-22s -> %18s %-22s" % (
+            s / max(len(its), 1), s / c, c, site_of(l0), func_of(l0)[:22], site_of(l1), func_of(l1)[:22]))
 
 # raw timeline of two leader iterations with the scouts' records interleaved
 w0 = int(os.environ.get("SMP_TRACE_W0", "20"))
@@ -94,5 +111,5 @@ for rl_, it_, ln_, ck_ in zip(role[sel][order], it[sel][order], line[sel][order]
     if ln_ >= TR_BAR0:
         print("  %8.2f  L  it+%d  %d barriers in the iteration" % ((ck_ - t0) * TICK_US, it_ - w0, ln_ - TR_BAR0))
         continue
-    print("  %8.2f  %s it+%d  %4d %s" % ((ck_ - t0) * TICK_US, "L " if rl_ == 0 else "S%d" % rl_, it_ - w0, ln_,
-                                         func_of(ln_)))
+    print("  %8.2f  %s it+%d  %18s %s" % ((ck_ - t0) * TICK_US, "L " if rl_ == 0 else "S%d" % rl_, it_ - w0, site_of(ln_),
+                                          func_of(ln_)))
