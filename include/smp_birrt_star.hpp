@@ -212,6 +212,94 @@ class BiRRTstarPlanner {
           "smp_set_disabled_map_links");
   }
 
+  // Not in the reference (birrt_star.h:411-414 keeps "Planning with Attached Objects" as a commented-out stub): after
+  // a grasp, the object -- spheres given in `link`'s frame, centres as rows of 3 -- becomes a collision link `name` of
+  // the planner's robot (smp_robot_attach + smp_planner_set_robot); every later check, plan and pass honours it.
+  // touch_links: collision links the object may overlap (no self pair with them).  Further objects stack.  False
+  // (nothing changed) when the library refuses the object: an unknown link, a name in use, a bad sphere, no capacity.
+  bool attachObject(const std::string& link, const vector<vector<double> >& centres, const vector<double>& radii,
+                    const std::string& name = "attached_object",
+                    const std::vector<std::string>& touch_links = std::vector<std::string>()) {
+    need();
+    if (centres.size() != radii.size()) return false;
+    vector<double> c;
+    for (size_t i = 0; i < centres.size(); ++i) {
+      if (centres[i].size() != 3) return false;
+      c.insert(c.end(), centres[i].begin(), centres[i].end());
+    }
+    std::vector<const char*> touch;
+    for (const std::string& t : touch_links) touch.push_back(t.c_str());
+    smp_attach a;
+    a.link = link.c_str();
+    a.name = name.c_str();
+    a.n_spheres = (int)radii.size();
+    a.centres = c.data();
+    a.radii = radii.data();
+    a.touch_links = touch.empty() ? nullptr : touch.data();
+    a.n_touch = (int)touch.size();
+    smp_robot* with = nullptr;
+    if (smp_robot_attach(robot_, &a, &with) != SMP_OK) return false;
+    const int st = smp_planner_set_robot(planner_, with);
+    if (st != SMP_OK) {
+      smp_robot_destroy(with);
+      check(st, "smp_planner_set_robot");
+    }
+    if (!detached_) detached_ = robot_;
+    else smp_robot_destroy(robot_);
+    robot_ = with;
+    return true;
+  }
+
+  // Not in the reference: attachObject for a bounding box -- half extents, placed in `link`'s frame by pose (12 values:
+  // R row-major, then p; empty: centred on the frame) -- covered by at most max_spheres spheres within tol
+  // (smp_cover_box).
+  bool attachBox(const std::string& link, const vector<double>& half, const vector<double>& pose = vector<double>(),
+                 double tol = 0.01, const std::string& name = "attached_object",
+                 const std::vector<std::string>& touch_links = std::vector<std::string>(), int max_spheres = 16) {
+    need();
+    if (half.size() != 3 || (!pose.empty() && pose.size() != 12) || max_spheres < 1) return false;
+    vector<double> c(3 * (size_t)max_spheres), r((size_t)max_spheres);
+    int n = 0;
+    if (smp_cover_box(half.data(), pose.empty() ? nullptr : pose.data(), tol, max_spheres, c.data(), r.data(), &n) != SMP_OK)
+      return false;
+    vector<vector<double> > centres;
+    for (int k = 0; k < n; ++k) centres.push_back(vector<double>(c.begin() + 3 * k, c.begin() + 3 * k + 3));
+    r.resize((size_t)n);
+    return attachObject(link, centres, r, name, touch_links);
+  }
+
+  // Not in the reference: after the release, the robot as it was before the first attachObject.
+  void detachObject() {
+    need();
+    if (!detached_) return;
+    check(smp_planner_set_robot(planner_, detached_), "smp_planner_set_robot");
+    smp_robot_destroy(robot_);
+    robot_ = detached_;
+    detached_ = nullptr;
+  }
+
+  // Not in the reference: before each setOctree, the pose the octomap was taken at (poseCurrent).  The octomap the node
+  // fetches holds the arm's voxels and a grasped object's; the robot's own volume at that pose -- every collision link,
+  // or `links`, e.g. the object's name -- grown by pad metres is then carved out of the map inside setOctree (on the
+  // GPU, smp_planner_set_carve).  An empty pose turns the filter off.
+  void setSelfFilter(const vector<double>& poseCurrent, double pad = 0.0,
+                     const std::vector<std::string>& links = std::vector<std::string>()) {
+    need();
+    if (poseCurrent.empty()) {
+      check(smp_planner_set_carve(planner_, nullptr), "smp_planner_set_carve");
+      return;
+    }
+    if (poseCurrent.size() != 8) throw std::runtime_error("smp: setSelfFilter needs a pose of 8 joints");
+    std::vector<const char*> names;
+    for (const std::string& l : links) names.push_back(l.c_str());
+    smp_carve c;
+    for (int j = 0; j < 8; ++j) c.q[j] = poseCurrent[(size_t)j];
+    c.pad = pad;
+    c.links = names.empty() ? nullptr : names.data();
+    c.n_links = (int)names.size();
+    check(smp_planner_set_carve(planner_, &c), "smp_planner_set_carve");
+  }
+
   // The node's keyframe loops over isConfigValid (fold / unfold arm, squirrel_8dof_planner.cpp:759-784, 814-823) as
   // one batched check: index of the first pose in collision, or -1 when all are valid.
   long long firstInvalidConfig(const vector<vector<double> >& configs, bool check_self_collision,
@@ -551,11 +639,14 @@ class BiRRTstarPlanner {
   void release() {
     if (planner_) smp_planner_destroy(planner_);
     if (robot_) smp_robot_destroy(robot_);
+    if (detached_) smp_robot_destroy(detached_);
     planner_ = nullptr;
     robot_ = nullptr;
+    detached_ = nullptr;
   }
 
   smp_robot* robot_ = nullptr;
+  smp_robot* detached_ = nullptr;  // the robot before attachObject, while an object is attached
   string urdf_, srdf_;
   smp_planner* planner_ = nullptr;
   smp_params params_;

@@ -6,6 +6,12 @@
  *   smp_robot_create_json      KDLRobotModel + CollisionChecker construction
  *                              (birrt_star.cpp:61-73, kdl_kuka_model.cpp:12-236, collision_checker.hpp:65-74)
  *   smp_robot_create_urdf      the same from robot_description / SRDF text (collision_checker.hpp:176-393)
+ *   smp_robot_attach           a grasped object as one more collision link of a robot (the reference keeps "Planning
+ *   smp_cover_box / _cylinder  with Attached Objects" as a commented-out stub, birrt_star.h:411-414), and sphere
+ *   smp_planner_set_robot      covers of a bounding box / cylinder; the planner's robot swapped in place, scene kept
+ *   smp_planner_set_carve      the self filter the node's octomap needs before setOctree (the fetched map holds the
+ *   smp_carve_keys             arm's and the grasped object's voxels): the robot's volume at the pose the map was
+ *   smp_planner_last_carve     taken carved out of the key list inside the device scene build, or as a mask
  *   smp_scene_from_keys        BiRRTstarPlanner::setOctree -> CollisionChecker::setOcTree
  *                              (birrt_star.cpp:1621-1624, collision_checker.hpp:76-88) for occupied leaf keys
  *   smp_scene_from_bt          the same from an octomap binary (.bt / binary octomap_msgs payload), with the
@@ -204,6 +210,46 @@ const char* smp_robot_link_name(const smp_robot* r, int i);
 int smp_robot_self_rounds(const smp_robot* r, int32_t info[8], uint16_t* sp_ab, double* sp_rr2, uint16_t* pp_ps,
                           int32_t* partner, double* rr2, uint32_t* prim_mask);
 
+/* Attached objects (not in the reference: birrt_star.h:411-414 keeps "Planning with Attached Objects" as a stub).
+ * A grasped object is one more collision link of the model, rigidly fixed to an existing link and covered by spheres
+ * given in that link's frame.  smp_robot_attach leaves `base` untouched and returns a new robot (release it with
+ * smp_robot_destroy); it composes, so a second object is attached to the result of the first.  The result is the
+ * robot smp_robot_create_json builds from base's model with these additions, byte for byte in the device model:
+ *   one link `name` after all links (parent `link`, fixed joint, identity frame); its spheres after all spheres, on
+ *   the parent's body, centres carried into the body frame by the model generator's own arithmetic; one link bound
+ *   (centre: componentwise mean, radius: max(distance + r) + 1e-6); one self pair (i, new) for every collision link i
+ *   on another body than the parent's that is not a touch link, the pair list kept in lexicographic order.  Links on
+ *   the parent's body are rigid to the object and get no pair, as everywhere else in the model.
+ * SMP_ERR_ARG: a NULL argument, an unknown `link`, a `name` some link already has, a touch link that is unknown or
+ * has no collision geometry, n_spheres < 1, a non-finite value, a radius <= 0 or > 0.45 m (the scene grids' padding),
+ * a base model without its link tree.  SMP_ERR_CAPACITY: more spheres, collision links, link pairs, sphere pairs or
+ * (primitive, sphere) pairs than the device model holds (72, 32, 256, 768, 320); for the committed robotino model
+ * that is reached beyond 16 spheres on the hand.  Past 64 spheres and primitives together the job tiles run two items
+ * per lane and the flat self lists instead of the self rounds (smp_robot_self_rounds, info[4] = 0): slower, same
+ * results. */
+typedef struct smp_attach {
+  const char* link;        /* existing link the object is rigidly fixed to, e.g. "hand_palm_link" */
+  const char* name;        /* name of the new collision link; must differ from every link name */
+  int n_spheres;           /* >= 1 */
+  const double* centres;   /* n x 3, in `link`'s frame */
+  const double* radii;     /* n, each finite, > 0 and <= 0.45 */
+  const char* const* touch_links; int n_touch;  /* collision links the object may overlap: no self pair with them */
+} smp_attach;
+int smp_robot_attach(const smp_robot* base, const smp_attach* a, smp_robot** out);
+/* Conservative cover of a box (half extents) or of a cylinder upright in its own frame (radius, half length along z)
+ * by at most max_spheres equal spheres on its longest axis (box: the lowest such axis; cylinder: z), for callers that
+ * hold a bounding volume.  With ha the half length on that axis and rho the square root of the sum of squares of the
+ * other two half extents (cylinder: the radius): m = min(max_spheres, max(1, ceil(ha / sqrt((rho + tol)^2 - rho^2))));
+ * centre k sits at -ha + (2k + 1) * (ha / m) on the axis; every radius is sqrt((ha / m)^2 + rho^2), so the spheres
+ * contain the volume for every m and overshoot it sideways by at most tol unless max_spheres caps m.  Every operation
+ * is rounded on its own.  The centres are then mapped by pose (R row-major, then p; NULL: identity) into the link's
+ * frame.  centres / radii hold max_spheres entries; *n receives m.  SMP_ERR_ARG: a NULL output, max_spheres < 1, a
+ * non-finite value, an extent, radius or tol <= 0. */
+int smp_cover_box(const double half[3], const double pose[12], double tol, int max_spheres,
+                  double* centres, double* radii, int* n);
+int smp_cover_cylinder(double radius, double half_length, const double pose[12], double tol, int max_spheres,
+                       double* centres, double* radii, int* n);
+
 int smp_scene_from_keys(const uint16_t* keys_xyz, int64_t n, const smp_scene_opts* opts, smp_scene** out);
 int smp_scene_from_bt(const uint8_t* data, size_t size, const smp_scene_opts* opts, smp_scene** out);
 /* Octomap full format (.ot): per node a float log-odds and a child-existence byte; leaves with log-odds >= 0 are
@@ -249,11 +295,52 @@ int smp_planner_set_scene_ot(smp_planner* p, const uint8_t* data, size_t size, c
 int smp_planner_set_scene_octomap_msg(smp_planner* p, const char* id, double resolution, int binary,
                                       const uint8_t* data, size_t size, const smp_scene_opts* opts,
                                       smp_scene_build* info);
+/* Self filter (not in the reference): the robot's own volume carved out of an occupied key list on the GPU.  The
+ * octomap the node fetches holds the arm's voxels and those of a grasped object, so the start pose is "in collision"
+ * against its own image.  Definition: take the key list after floor insertion; its grid geometry (key of cell
+ * (0, 0, 0), dims, origin o) is exactly what smp_planner_set_scene_keys computes for that list before any carving.
+ * Key k sits at cell i = k - kmin, the box [o + i * res, o + (i + 1) * res] per axis.  With the world items of the
+ * selected collision links at q formed as the checker forms them, k is carved iff some item's "Clearance queries" map
+ * term against that single cell is <= pad: fl(fl(sqrt(gx^2 + gy^2 + gz^2)) - r) <= pad for a sphere, that section's
+ * box or cylinder term for a primitive.  The comparison is non-strict, the exact complement of the margin checks'
+ * strict >: after carving every link at (q, pad), smp_check_configs_margin(q, {pad, 0}) is clear of the map and
+ * smp_clearance_configs(q, D).map > pad.  The link selection is independent of smp_set_disabled_map_links; links =
+ * NULL / n_links = 0 selects every collision link, attached ones included.
+ *   smp_carve_keys        one flag per caller key (1: carved).  Floor keys (opts->insert_floor) take part in the
+ *                         geometry only.  n = 0: SMP_OK.
+ *   smp_planner_set_carve the sticky form (copied; NULL turns it off): smp_planner_set_scene_keys, _bt, _ot and
+ *                         _octomap_msg then clear the bits of the carved keys (floor keys included) between the
+ *                         scatter of the keys and everything derived from the bit grid, so bricks, n_occupied,
+ *                         dilation, distance fields and slabs see the carved occupancy; bbox_min / bbox_max stay
+ *                         those of the full list.  The links are resolved by name at every build (the robot may
+ *                         have been swapped since); on an error the planner keeps its previous scene.
+ *                         smp_planner_set_scene and smp_planner_set_scene_device do not carve.
+ *   smp_planner_last_carve  carved keys and timing of the last carving build or smp_carve_keys call.
+ * SMP_ERR_ARG: a NULL planner or carve (smp_carve_keys), a non-finite q, a pad that is not finite or negative, a link
+ * that is unknown or has no collision geometry, a non-positive resolution. */
+typedef struct smp_carve {
+  double q[8];                                /* the robot's pose when the map was taken */
+  double pad;                                 /* metres; finite, >= 0 */
+  const char* const* links; int n_links;      /* collision links to carve; 0 = every collision link, attached ones too */
+} smp_carve;
+typedef struct smp_carve_info { int64_t n_carved; double kernel_ms, total_ms; } smp_carve_info;  /* may be NULL */
+int smp_planner_set_carve(smp_planner* p, const smp_carve* c);
+int smp_planner_last_carve(const smp_planner* p, smp_carve_info* info);
+int smp_carve_keys(smp_planner* p, const uint16_t* keys_xyz, int64_t n, const smp_scene_opts* opts,
+                   const smp_carve* c, uint8_t* carved, smp_carve_info* info);
 /* Planner parameters for subsequent smp_plan calls (activate/deactivateTreeOptimization,
  * activate/deactivateInformedSampling, birrt_star.h:57-63; setEdgeCostWeights keeps weights 1). */
 int smp_planner_set_params(smp_planner* p, const smp_params* params);
 int smp_planner_get_params(const smp_planner* p, smp_params* params);
 int smp_set_disabled_map_links(smp_planner* p, const char* const* link_names, int n);
+/* Swaps the planner's robot in place (not in the reference): after a grasp smp_planner_set_robot(p, attached), after
+ * the release smp_planner_set_robot(p, base).  The device model is uploaded again (the SMP_SELF_FLAT override
+ * included), the disabled-link set is kept by name (the object's own name may be in it) and the scene stays: its
+ * byte field exists only while every sphere threshold is below 255, so it is derived from the box-gap field by one
+ * kernel, or dropped, when the new spheres change that.  Trees and query buffers are untouched.  SMP_ERR_ARG: a NULL
+ * argument, or a scene is set and the new robot's primitive tables (count, types, bodies, frames, extents) differ
+ * from the current ones -- the slab fields belong to the primitives; attaching never changes them. */
+int smp_planner_set_robot(smp_planner* p, const smp_robot* r);
 
 /* Multi-GPU (queries shard, the scene is sent once per scene, no per-iteration collective).
  * The device-resident form of a planner's scene: the arrays smp_planner_set_scene derived for the planner's robot

@@ -94,6 +94,22 @@ class SceneBuild(ctypes.Structure):
                 ("bbox_max", _d * 3), ("kernel_ms", _d), ("total_ms", _d)]
 
 
+class Attach(ctypes.Structure):
+    """smp_attach: a grasped object as spheres in the frame of the link it is fixed to."""
+    _fields_ = [("link", ctypes.c_char_p), ("name", ctypes.c_char_p), ("n_spheres", _i), ("centres", _pd),
+                ("radii", _pd), ("touch_links", ctypes.POINTER(ctypes.c_char_p)), ("n_touch", _i)]
+
+
+class Carve(ctypes.Structure):
+    """smp_carve: the self filter -- the pose the map was taken at, the pad, the collision links to carve."""
+    _fields_ = [("q", _d * 8), ("pad", _d), ("links", ctypes.POINTER(ctypes.c_char_p)), ("n_links", _i)]
+
+
+class CarveInfo(ctypes.Structure):
+    """smp_carve_info: carved keys and timing of the last carve."""
+    _fields_ = [("n_carved", _i64), ("kernel_ms", _d), ("total_ms", _d)]
+
+
 class ShortcutInfo(ctypes.Structure):
     """smp_shortcut_info: counts, costs and timing of one smp_shortcut_path call."""
     _fields_ = [("n_edges", _i64), ("n_valid", _i64), ("configs_checked", _i64), ("cost_in", _d), ("cost_out", _d),
@@ -154,6 +170,14 @@ EXPORTS = [
     ("smp_robot_num_links", _i, [_p]),
     ("smp_robot_link_name", ctypes.c_char_p, [_p, _i]),
     ("smp_robot_self_rounds", _i, [_p, _p, _p, _p, _p, _p, _p, _p]),
+    ("smp_robot_attach", _i, [_p, ctypes.POINTER(Attach), ctypes.POINTER(_p)]),
+    ("smp_cover_box", _i, [_pd, _pd, _d, _i, _pd, _pd, ctypes.POINTER(_i)]),
+    ("smp_cover_cylinder", _i, [_d, _d, _pd, _d, _i, _pd, _pd, ctypes.POINTER(_i)]),
+    ("smp_planner_set_robot", _i, [_p, _p]),
+    ("smp_planner_set_carve", _i, [_p, ctypes.POINTER(Carve)]),
+    ("smp_planner_last_carve", _i, [_p, ctypes.POINTER(CarveInfo)]),
+    ("smp_carve_keys", _i, [_p, _p, _i64, ctypes.POINTER(SceneOpts), ctypes.POINTER(Carve), _p,
+                            ctypes.POINTER(CarveInfo)]),
     ("smp_scene_from_keys", _i, [_p, _i64, ctypes.POINTER(SceneOpts), ctypes.POINTER(_p)]),
     ("smp_scene_from_bt", _i, [_p, ctypes.c_size_t, ctypes.POINTER(SceneOpts), ctypes.POINTER(_p)]),
     ("smp_scene_from_ot", _i, [_p, ctypes.c_size_t, ctypes.POINTER(SceneOpts), ctypes.POINTER(_p)]),

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "smp_attach.h"
 #include "smp_kernels.h"
 #include "smp_math.h"
 #include "smp_planner.h"
@@ -43,6 +44,47 @@ static int update_mapcfg(smp_planner* p) {
   HIPCHK(hipMemcpyAsync(p->d_mc, &p->mc_host, sizeof(MapCfg), hipMemcpyHostToDevice, p->stream));
   HIPCHK(hipStreamSynchronize(p->stream));
   return SMP_OK;
+}
+
+// The self filter's link selection as a mask over the robot's collision links (n = 0: all of them); SMP_ERR_ARG for a
+// link that is unknown or has no collision geometry.
+static int carve_link_mask(const RobotHost& h, const char* const* links, int n, uint32_t* mask) {
+  if (n < 0 || (n > 0 && !links)) return SMP_ERR_ARG;
+  if (n == 0) {
+    *mask = (uint32_t)((1ull << h.dev.n_clink) - 1ull);
+    return SMP_OK;
+  }
+  uint32_t m = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!links[i]) return SMP_ERR_ARG;
+    int c = -1;
+    for (size_t l = 0; l < h.link_names.size(); ++l)
+      if (h.link_names[l] == links[i]) c = h.clink_of_link[l];
+    if (c < 0) return SMP_ERR_ARG;
+    m |= 1u << c;
+  }
+  *mask = m;
+  return SMP_OK;
+}
+
+static bool carve_values_ok(const smp_carve* c) {
+  for (int j = 0; j < NJ; ++j)
+    if (!std::isfinite(c->q[j])) return false;
+  return std::isfinite(c->pad) && c->pad >= 0.0;
+}
+
+// Scratch and events of the carve launches, created on first use.
+static hipError_t carve_scratch(smp_planner* p) {
+  hipError_t e;
+  if ((e = p->d_citems.reserve(1)) != hipSuccess || (e = p->d_ccount.reserve(1)) != hipSuccess) return e;
+  if (!p->ev2 && (e = hipEventCreate(&p->ev2)) != hipSuccess) return e;
+  if (!p->ev3 && (e = hipEventCreate(&p->ev3)) != hipSuccess) return e;
+  return hipSuccess;
+}
+
+static void self_flat_override(RobotDev* d) {
+  if (const char* e = std::getenv("SMP_SELF_FLAT"))
+    if (std::atoi(e) != 0) d->sr_ok = 0;
 }
 
 extern "C" {
@@ -106,6 +148,18 @@ int smp_robot_create_urdf(const char* urdf_xml, const char* srdf_xml, const char
     fprintf(stderr, "smp_gpu: %s\n", e.what());
     delete r;
     return SMP_ERR_PARSE;
+  }
+  *out = r;
+  return SMP_OK;
+}
+
+int smp_robot_attach(const smp_robot* base, const smp_attach* a, smp_robot** out) {
+  if (!base || !a || !out) return SMP_ERR_ARG;
+  smp_robot* r = new smp_robot();
+  const int st = robot_attach(base->h, *a, &r->h);
+  if (st != SMP_OK) {
+    delete r;
+    return st;
   }
   *out = r;
   return SMP_OK;
@@ -277,6 +331,7 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
     need = std::max(need, repair_kernels_private_bytes());
     need = std::max(need, clearance_kernels_private_bytes());
     need = std::max(need, margin_kernels_private_bytes());
+    need = std::max(need, carve_kernels_private_bytes());
     size_t cur = 0;
     if (hipDeviceGetLimit(&cur, hipLimitStackSize) == hipSuccess && cur < need) {
       need = (need + 255) / 256 * 256;
@@ -288,8 +343,7 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
   }
   // SMP_SELF_FLAT: the job tiles of this planner run the flat self-pair lists, as for a model that does not qualify
   // for the rounds (experiments, and the parity test of the two forms); the planner's copy of the model only
-  if (const char* e = std::getenv("SMP_SELF_FLAT"))
-    if (std::atoi(e) != 0) p->robot.dev.sr_ok = 0;
+  self_flat_override(&p->robot.dev);
   // every failure from here on releases what was created so far (smp_planner_destroy skips null handles)
   if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&p->d_rb, sizeof(RobotDev)) != hipSuccess || hipMalloc(&p->d_mc, sizeof(MapCfg)) != hipSuccess ||
@@ -336,6 +390,9 @@ void smp_planner_destroy(smp_planner* p) {
   if (p->d_mc) (void)hipFree(p->d_mc);
   if (p->ev0) (void)hipEventDestroy(p->ev0);
   if (p->ev1) (void)hipEventDestroy(p->ev1);
+  p->d_citems.release(); p->d_cflags.release(); p->d_ccount.release();
+  if (p->ev2) (void)hipEventDestroy(p->ev2);
+  if (p->ev3) (void)hipEventDestroy(p->ev3);
   if (p->stream) (void)hipStreamDestroy(p->stream);
   if (p->h_ttff) (void)hipHostFree(p->h_ttff);
   if (p->h_trace) (void)hipHostFree(p->h_trace);
@@ -437,6 +494,16 @@ static int set_scene_keys_device(smp_planner* p, const uint16_t* keys, int64_t n
       fprintf(stderr, "smp_gpu: primitive reach %.3f m exceeds the grid padding\n", d.prim_rxy[k]);
       return SMP_ERR_ARG;
     }
+  // the self filter's links, by name against the robot of this build (before anything of the old scene is touched)
+  uint32_t carve_mask = 0;
+  if (p->carve_on) {
+    std::vector<const char*> names;
+    for (const std::string& s : p->carve_links) names.push_back(s.c_str());
+    if (carve_link_mask(p->robot, names.data(), (int)names.size(), &carve_mask) != SMP_OK) {
+      fprintf(stderr, "smp_gpu: the self filter names a link the planner's robot does not have (smp_planner_set_carve)\n");
+      return SMP_ERR_ARG;
+    }
+  }
   int nx = 1, ny = 1, nz = 1, kmin[3] = {0, 0, 0};
   double org[3] = {0.0, 0.0, 0.0 + z_offset}, bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
   if (n > 0) {
@@ -500,11 +567,31 @@ static int set_scene_keys_device(smp_planner* p, const uint16_t* keys, int64_t n
   a.d2 = p->d_d2.p;
   a.d2b = bytes ? p->d_d2b.p : nullptr;
   a.n_prim = d.n_prim; a.k01 = p->d_sk01.p; a.slab = p->d_slab.p;
+  CarveArgs ca{};
+  const bool carving = p->carve_on && n > 0;
+  if (carving) {
+    HIPCHK(carve_scratch(p));
+    ca.rb = p->d_rb;
+    for (int j = 0; j < NJ; ++j) ca.q[j] = p->carve_q[j];
+    ca.pad = p->carve_pad;
+    ca.links = carve_mask;
+    ca.items = p->d_citems.p;
+    ca.keys = p->d_keys.p; ca.n_keys = n;
+    for (int c = 0; c < 3; ++c) { ca.kmin[c] = kmin[c]; ca.org[c] = org[c]; }
+    ca.res = res;
+    ca.flags = nullptr;
+    ca.bits = p->d_sbits.p;
+    ca.nx = nx; ca.ny = ny; ca.nz = nz;
+    ca.count = p->d_ccount.p;
+    a.carve = &ca;
+    a.carve_ev[0] = p->ev2; a.carve_ev[1] = p->ev3;
+  }
   HIPCHK(hipEventRecord(p->ev0, p->stream));
   HIPCHK(launch_scene_build(p->stream, a));
   HIPCHK(hipEventRecord(p->ev1, p->stream));
-  unsigned long long n_occ = 0;
+  unsigned long long n_occ = 0, n_carved = 0;
   HIPCHK(hipMemcpyAsync(&n_occ, p->d_scount.p, sizeof(n_occ), hipMemcpyDeviceToHost, p->stream));
+  if (carving) HIPCHK(hipMemcpyAsync(&n_carved, p->d_ccount.p, sizeof(n_carved), hipMemcpyDeviceToHost, p->stream));
   p->sc.nx = nx; p->sc.ny = ny; p->sc.nz = nz;
   p->sc.bnx = bnx; p->sc.bny = bny;
   p->sc.ox = org[0]; p->sc.oy = org[1]; p->sc.oz = org[2]; p->sc.res = res; p->sc.inv_res = 1.0 / res;
@@ -519,6 +606,13 @@ static int set_scene_keys_device(smp_planner* p, const uint16_t* keys, int64_t n
   if (int st = update_mapcfg(p)) return st;
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+  if (p->carve_on) {
+    float cms = 0.f;
+    if (carving) HIPCHK(hipEventElapsedTime(&cms, p->ev2, p->ev3));
+    p->last_carve.n_carved = (int64_t)n_carved;
+    p->last_carve.kernel_ms = cms;
+    p->last_carve.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
   if (info) {
     info->dims[0] = nx; info->dims[1] = ny; info->dims[2] = nz;
     for (int c = 0; c < 3; ++c) { info->origin[c] = org[c]; info->bbox_min[c] = bmin[c]; info->bbox_max[c] = bmax[c]; }
@@ -538,6 +632,101 @@ int smp_planner_set_scene_keys(smp_planner* p, const uint16_t* keys, int64_t n, 
   std::vector<uint16_t> k(keys, keys + 3 * std::max<int64_t>(n, 0));
   floor_keys(o->floor_center[0], o->floor_center[1], o->resolution, o->floor_distance, &k);
   return set_scene_keys_device(p, k.data(), (int64_t)k.size() / 3, o->resolution, o->z_offset, info, t0);
+}
+
+int smp_planner_set_carve(smp_planner* p, const smp_carve* c) {
+  if (!p) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  if (!c) {
+    p->carve_on = false;
+    p->carve_links.clear();
+    return SMP_OK;
+  }
+  uint32_t mask = 0;
+  if (!carve_values_ok(c) || carve_link_mask(p->robot, c->links, c->n_links, &mask) != SMP_OK) return SMP_ERR_ARG;
+  p->carve_on = true;
+  for (int j = 0; j < NJ; ++j) p->carve_q[j] = c->q[j];
+  p->carve_pad = c->pad;
+  p->carve_links.clear();
+  for (int i = 0; i < c->n_links; ++i) p->carve_links.push_back(c->links[i]);
+  return SMP_OK;
+}
+
+int smp_planner_last_carve(const smp_planner* p, smp_carve_info* info) {
+  if (!p || !info) return SMP_ERR_ARG;
+  *info = p->last_carve;
+  return SMP_OK;
+}
+
+// The self filter as a mask over the caller's keys.  The grid geometry is set_scene_keys_device's own arithmetic on the
+// list after floor insertion; the planner's scene is not touched (the keys share the build's upload buffer, which holds
+// nothing between builds).
+int smp_carve_keys(smp_planner* p, const uint16_t* keys, int64_t n, const smp_scene_opts* o, const smp_carve* c,
+                   uint8_t* carved, smp_carve_info* info) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!p || !o || !c || n < 0 || (n > 0 && (!keys || !carved)) || !(o->resolution > 0)) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  uint32_t mask = 0;
+  if (!carve_values_ok(c) || carve_link_mask(p->robot, c->links, c->n_links, &mask) != SMP_OK) return SMP_ERR_ARG;
+  p->last_carve = smp_carve_info{0, 0.0, 0.0};
+  if (info) *info = p->last_carve;
+  if (n == 0) return SMP_OK;
+  const double res = o->resolution;
+  std::vector<uint16_t> fk;
+  if (o->insert_floor) floor_keys(o->floor_center[0], o->floor_center[1], res, o->floor_distance, &fk);
+  int kmin[3] = {1 << 30, 1 << 30, 1 << 30}, kmax[3] = {-1, -1, -1};
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const int k = keys[i * 3 + a];
+      kmin[a] = std::min(kmin[a], k);
+      kmax[a] = std::max(kmax[a], k);
+    }
+  for (size_t i = 0; i < fk.size() / 3; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const int k = fk[i * 3 + a];
+      kmin[a] = std::min(kmin[a], k);
+      kmax[a] = std::max(kmax[a], k);
+    }
+  const int pad = grid_pad_cells(res);
+  CarveArgs ca{};
+  for (int a = 0; a < 3; ++a) {
+    kmin[a] -= pad;
+    kmax[a] += pad;
+    ca.kmin[a] = kmin[a];
+  }
+  ca.org[0] = (double)(kmin[0] - KEY_OFFSET) * res;
+  ca.org[1] = (double)(kmin[1] - KEY_OFFSET) * res;
+  ca.org[2] = (double)(kmin[2] - KEY_OFFSET) * res + o->z_offset;
+  ca.nx = kmax[0] - kmin[0] + 1; ca.ny = kmax[1] - kmin[1] + 1; ca.nz = kmax[2] - kmin[2] + 1;
+  ca.res = res;
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(carve_scratch(p));
+  HIPCHK(p->d_keys.reserve((size_t)n * 3));
+  HIPCHK(p->d_cflags.reserve((size_t)n));
+  HIPCHK(hipMemcpyAsync(p->d_keys.p, keys, (size_t)n * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, p->stream));
+  ca.rb = p->d_rb;
+  for (int j = 0; j < NJ; ++j) ca.q[j] = c->q[j];
+  ca.pad = c->pad;
+  ca.links = mask;
+  ca.items = p->d_citems.p;
+  ca.keys = p->d_keys.p; ca.n_keys = n;
+  ca.flags = p->d_cflags.p;
+  ca.bits = nullptr;
+  ca.count = p->d_ccount.p;
+  HIPCHK(hipEventRecord(p->ev2, p->stream));
+  HIPCHK(launch_carve(p->stream, ca));
+  HIPCHK(hipEventRecord(p->ev3, p->stream));
+  unsigned long long n_carved = 0;
+  HIPCHK(hipMemcpyAsync(carved, p->d_cflags.p, (size_t)n, hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipMemcpyAsync(&n_carved, p->d_ccount.p, sizeof(n_carved), hipMemcpyDeviceToHost, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, p->ev2, p->ev3));
+  p->last_carve.n_carved = (int64_t)n_carved;
+  p->last_carve.kernel_ms = ms;
+  p->last_carve.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (info) *info = p->last_carve;
+  return SMP_OK;
 }
 
 // Occupied keys + free leaves of an octomap stream (the host decoders: the octree walk is sequential and small, and
@@ -704,6 +893,50 @@ int smp_set_disabled_map_links(smp_planner* p, const char* const* names, int n) 
   HIPCHK(hipSetDevice(p->device));
   p->disabled.clear();
   for (int i = 0; i < n; ++i) if (names[i]) p->disabled.insert(names[i]);
+  return update_mapcfg(p);
+}
+
+// The planner's robot swapped in place (an object attached or detached, smp_robot_attach).  Every kernel reads the
+// model from d_rb and the per-sphere map constants from d_mc, so the swap is those two uploads; of the scene only the
+// byte field depends on the spheres (it exists while every threshold is below 255), and the slab fields belong to
+// the primitives, which therefore may not change under a scene.
+int smp_planner_set_robot(smp_planner* p, const smp_robot* r) {
+  if (!p || !r) return SMP_ERR_ARG;
+  if (int b_ = busy_check(p)) return b_;
+  const RobotDev& o = p->robot.dev;
+  const RobotDev& d = r->h.dev;
+  if (p->have_scene) {
+    const bool same = d.n_prim == o.n_prim && !std::memcmp(d.prim_type, o.prim_type, sizeof(o.prim_type)) &&
+                      !std::memcmp(d.prim_body, o.prim_body, sizeof(o.prim_body)) &&
+                      !std::memcmp(d.prim_cb, o.prim_cb, sizeof(o.prim_cb)) &&
+                      !std::memcmp(d.prim_ab, o.prim_ab, sizeof(o.prim_ab)) &&
+                      !std::memcmp(d.prim_h, o.prim_h, sizeof(o.prim_h)) &&
+                      !std::memcmp(d.prim_rxy, o.prim_rxy, sizeof(o.prim_rxy));
+    if (!same) {
+      fprintf(stderr, "smp_gpu: the new robot's primitives differ from the scene's slab fields (set the scene again)\n");
+      return SMP_ERR_ARG;
+    }
+  }
+  HIPCHK(hipSetDevice(p->device));
+  const uint8_t* d2b = p->sc.d2b;
+  if (p->have_scene) {
+    uint32_t tmax = 0;
+    for (int k = 0; k < d.n_sph; ++k) tmax = std::max(tmax, sphere_threshold(d.sph_r[k], p->scene_res));
+    if (tmax >= 255) {
+      d2b = nullptr;
+    } else if (!d2b) {
+      const size_t nc = (size_t)p->sc.nx * p->sc.ny * p->sc.nz;
+      HIPCHK(p->d_d2b.reserve(nc));
+      HIPCHK(launch_scene_bytes(p->stream, p->sc.d2, (long long)nc, p->d_d2b.p));
+      d2b = p->d_d2b.p;
+    }
+  }
+  RobotHost nh = r->h;
+  self_flat_override(&nh.dev);
+  HIPCHK(hipMemcpyAsync(p->d_rb, &nh.dev, sizeof(RobotDev), hipMemcpyHostToDevice, p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream));  // nh is pageable host memory and moves below
+  p->robot = std::move(nh);
+  p->sc.d2b = d2b;
   return update_mapcfg(p);
 }
 

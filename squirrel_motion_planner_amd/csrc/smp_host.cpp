@@ -26,6 +26,34 @@ static void copy3(const json::Value& v, double* o, int n = 3) {
   for (int i = 0; i < n; ++i) o[i] = v[i].d();
 }
 
+// The tree behind the collapse (RobotHost::link_*), when the model carries a well-formed one: every link with its
+// parent (preceding it), joint and fixed frame.  Anything else leaves has_tree false and the model loads as it always
+// did; only smp_robot_attach needs the tree.
+static void read_tree(const json::Value& m, RobotHost* out) {
+  out->has_tree = false;
+  out->link_parent.clear(); out->link_joint.clear(); out->link_R.clear(); out->link_p.clear(); out->bodies.clear();
+  try {
+    const json::Value& links = m["links"];
+    const size_t n = links.size();
+    if (n == 0) return;
+    std::vector<int> parent(n), joint(n), bodies;
+    std::vector<double> R(n * 9), p(n * 3);
+    for (size_t i = 0; i < n; ++i) {
+      if (!links[i].has("parent") || !links[i].has("joint") || !links[i].has("R") || !links[i].has("p")) return;
+      parent[i] = links[i]["parent"].i();
+      joint[i] = links[i]["joint"].i();
+      if (parent[i] < -1 || parent[i] >= (int)i) return;
+      copy3(links[i]["R"], &R[i * 9], 9);
+      copy3(links[i]["p"], &p[i * 3]);
+    }
+    for (size_t b = 0; b < m["bodies"].size(); ++b) bodies.push_back(m["bodies"][b].i());
+    out->link_parent.swap(parent); out->link_joint.swap(joint); out->link_R.swap(R); out->link_p.swap(p);
+    out->bodies.swap(bodies);
+    out->has_tree = true;
+  } catch (const std::exception&) {
+  }
+}
+
 // Robot model JSON (tools/gen_robot_model.py).  Mirrors KDLRobotModel + CollisionChecker construction.
 void robot_from_json(const std::string& text, RobotHost* out) {
   const json::Value m = json::parse(text.c_str());
@@ -40,6 +68,7 @@ void robot_from_model_value(const json::Value& m, RobotHost* out) {
   const json::Value& links = m["links"];
   out->link_names.clear();
   for (size_t i = 0; i < links.size(); ++i) out->link_names.push_back(links[i]["name"].s());
+  read_tree(m, out);
   const json::Value& bc = m["body_chain"];
   d.n_chain = (int)bc.size();
   if (d.n_chain > MAX_CHAIN) throw std::runtime_error("model: body chain too long");

@@ -12,6 +12,13 @@ struct RobotHost {
   RobotDev dev;
   std::vector<std::string> link_names;  // all tree links
   std::vector<int> clink_of_link;       // -1 if the link has no collision geometry
+  // the collision tree the model was collapsed from (kept for smp_robot_attach, smp_attach.h): per tree link its
+  // parent (-1: root), its planning joint (-1: fixed) and the fixed frame (R row-major, p) to its parent; bodies[b]
+  // is the tree link of body b.  Empty when the model text gives no tree (has_tree false).
+  bool has_tree = false;
+  std::vector<int> link_parent, link_joint;
+  std::vector<double> link_R, link_p;
+  std::vector<int> bodies;
 };
 
 struct SceneHost {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/smp_gpu.h"
+#include "smp_carve.h"
 #include "smp_clearance.h"
 #include "smp_pass.h"
 #include "smp_host.h"
@@ -127,6 +128,17 @@ struct smp_planner {
   // margin checks (smp_check_configs_margin): per-configuration results; the rows are d_clq, the other tables those of
   // the plain passes
   smp::DBuf<uint8_t> d_mclear;
+  // self filter (smp_planner_set_carve / smp_carve_keys): the sticky carve of the device scene builds, its links by
+  // name (resolved against the robot at every build), and the carve launches' scratch: the world items, the flags of
+  // the standalone call, the carved-key count; ev2 / ev3 time the carve launches inside a build
+  bool carve_on = false;
+  double carve_q[smp::NJ] = {0}, carve_pad = 0.0;
+  std::vector<std::string> carve_links;
+  smp::DBuf<smp::CarveItems> d_citems;
+  smp::DBuf<uint8_t> d_cflags;
+  smp::DBuf<unsigned long long> d_ccount;
+  hipEvent_t ev2 = nullptr, ev3 = nullptr;
+  smp_carve_info last_carve{0, 0.0, 0.0};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   double last_check_ms = 0, last_plan_ms = 0;
   int64_t last_plan_launches = 0;

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "smp_carve.h"
+
 namespace smp {
 
 struct SceneBuildArgs {
@@ -21,6 +23,11 @@ struct SceneBuildArgs {
   int n_prim;
   const int* k01;             // device, n_prim x (k0, k1): the layers each primitive's slab projects
   uint16_t* slab;
+  // self filter (smp_carve.h), nullptr: none.  Its launches run after the scatter of the keys and clear the carved
+  // keys' bits, so every derived array sees the carved occupancy; hipEventRecord of ev[0] / ev[1] (when given) brackets
+  // them on the stream.
+  const CarveArgs* carve = nullptr;
+  hipEvent_t carve_ev[2] = {nullptr, nullptr};
 };
 
 // Whether the passes can stage this grid's lines in LDS and index their launches (false: lines of more than 32768
@@ -30,6 +37,9 @@ bool scene_build_fits(int nx, int ny, int nz, int n_prim);
 size_t scene_words(int nx, int ny, int nz, int n_prim);
 // Enqueues every pass on `st`; no synchronisation.
 hipError_t launch_scene_build(hipStream_t st, const SceneBuildArgs& a);
+// The byte copy min(d2, 255) of n cells of a finished box-gap field (both device arrays, as hipMalloc aligns them);
+// enqueued on `st`, no synchronisation.
+hipError_t launch_scene_bytes(hipStream_t st, const uint16_t* d2, long long n, uint8_t* d2b);
 size_t scene_kernels_private_bytes();
 
 }  // namespace smp

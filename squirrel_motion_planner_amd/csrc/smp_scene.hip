@@ -183,6 +183,25 @@ __global__ __launch_bounds__(SB) void scene_edt_line_kernel(uint16_t* __restrict
   }
 }
 
+// The byte copy min(f, 255) of a finished field (smp_planner_set_robot, when a robot swap makes the copy valid for a
+// scene built without it): eight cells per work-item where the count allows, the tail cell by cell.
+__global__ __launch_bounds__(SB) void scene_bytes_kernel(const uint16_t* __restrict__ f, long long n,
+                                                         uint8_t* __restrict__ fb) {
+  const long long n8 = n >> 3;
+  for (long long i = (long long)blockIdx.x * SB + threadIdx.x; i < n8; i += (long long)gridDim.x * SB) {
+    const uint4 v = reinterpret_cast<const uint4*>(f)[i];
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    unsigned o[2] = {0u, 0u};
+    for (int k = 0; k < 4; ++k) {
+      const unsigned lo = w[k] & 0xffffu, hi = w[k] >> 16;
+      o[k >> 1] |= ((lo < 255u ? lo : 255u) | ((hi < 255u ? hi : 255u) << 8)) << ((k & 1) * 16);
+    }
+    reinterpret_cast<uint2*>(fb)[i] = make_uint2(o[0], o[1]);
+  }
+  if (blockIdx.x == 0)
+    for (long long c = (n8 << 3) + threadIdx.x; c < n; c += SB) fb[c] = (uint8_t)(f[c] < 255u ? f[c] : 255u);
+}
+
 // log2 of the widest x tile (64 .. 1 columns) whose L-cell lines fit the dynamic LDS; -1 if none does.
 int tile_log2(int L) {
   for (int t = 6; t >= 0; --t)
@@ -234,6 +253,11 @@ hipError_t launch_scene_build(hipStream_t st, const SceneBuildArgs& a) {
                        a.kmin[1], a.kmin[2], nx, ny, nz, wx, a.bits);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
+  if (a.carve) {
+    if (a.carve_ev[0] && (e = hipEventRecord(a.carve_ev[0], st)) != hipSuccess) return e;
+    if ((e = launch_carve(st, *a.carve)) != hipSuccess) return e;
+    if (a.carve_ev[1] && (e = hipEventRecord(a.carve_ev[1], st)) != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(scene_bricks_kernel, dim3(grid_for((long long)bnx * bny * bnz)), dim3(SB), 0, st, a.bits, ny, nz,
                      wx, bnx, bny, bnz, a.bricks, a.count);
   if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -259,12 +283,18 @@ hipError_t launch_scene_build(hipStream_t st, const SceneBuildArgs& a) {
   return hipSuccess;
 }
 
+hipError_t launch_scene_bytes(hipStream_t st, const uint16_t* d2, long long n, uint8_t* d2b) {
+  hipLaunchKernelGGL(scene_bytes_kernel, dim3(grid_for((n >> 3) + 1)), dim3(SB), 0, st, d2, n, d2b);
+  return hipGetLastError();
+}
+
 size_t scene_kernels_private_bytes() {
   size_t need = 0;
   hipFuncAttributes fa;
   const void* ks[] = {reinterpret_cast<const void*>(&scene_scatter_kernel), reinterpret_cast<const void*>(&scene_bricks_kernel),
                       reinterpret_cast<const void*>(&scene_project_kernel), reinterpret_cast<const void*>(&scene_dilate_kernel),
-                      reinterpret_cast<const void*>(&scene_edt_x_kernel), reinterpret_cast<const void*>(&scene_edt_line_kernel)};
+                      reinterpret_cast<const void*>(&scene_edt_x_kernel), reinterpret_cast<const void*>(&scene_edt_line_kernel),
+                      reinterpret_cast<const void*>(&scene_bytes_kernel)};
   for (const void* k : ks)
     if (hipFuncGetAttributes(&fa, k) == hipSuccess && (size_t)fa.localSizeBytes > need) need = fa.localSizeBytes;
   return need;

@@ -671,6 +671,10 @@ void robot_from_urdf(const std::string& urdf_text, const std::string& srdf_text,
   for (const TreeLink& t : tree) {
     json::Value v = obj();
     v.obj["name"] = str(t.name);
+    v.obj["parent"] = num(t.parent);
+    v.obj["joint"] = num(t.joint);
+    v.obj["R"] = nums(t.f.R, 9);
+    v.obj["p"] = nums(t.f.p, 3);
     tree_v.arr.push_back(v);
   }
   json::Value bodies_v = arr();

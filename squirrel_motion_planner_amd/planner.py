@@ -62,10 +62,65 @@ class Robot:
         n = lib().smp_robot_num_links(self.h)
         return [lib().smp_robot_link_name(self.h, i).decode() for i in range(n)]
 
+    def attach(self, link, centres, radii, name="attached_object", touch_links=()):
+        """smp_robot_attach: a new Robot with a grasped object as one more collision link `name`, rigidly fixed to
+        `link` and covered by spheres (centres (n, 3) in `link`'s frame, radii (n,)); no self pair with touch_links.
+        This robot is untouched, and the result can take a further object."""
+        c = np.ascontiguousarray(np.asarray(centres, np.float64).reshape(-1, 3))
+        r = np.ascontiguousarray(np.asarray(radii, np.float64).reshape(-1))
+        if len(c) != len(r):
+            raise ValueError("attach: %d centres but %d radii" % (len(c), len(r)))
+        touch = [t.encode() for t in touch_links]
+        a = L.Attach()
+        a.link, a.name, a.n_spheres = link.encode(), name.encode(), len(r)
+        a.centres, a.radii = c.ctypes.data_as(_pd), r.ctypes.data_as(_pd)
+        a.touch_links, a.n_touch = (ctypes.c_char_p * max(len(touch), 1))(*touch), len(touch)
+        h = ctypes.c_void_p()
+        check(lib().smp_robot_attach(self.h, ctypes.byref(a), ctypes.byref(h)), "smp_robot_attach")
+        return Robot(_handle=h)
+
+    def self_rounds_info(self):
+        """smp_robot_self_rounds' info: n_sph, n_prim, n_spairs, n_ppairs, qualifies, rounds, lanes, max_rounds."""
+        info = (ctypes.c_int32 * 8)()
+        check(lib().smp_robot_self_rounds(self.h, info, None, None, None, None, None, None), "smp_robot_self_rounds")
+        return dict(zip(("n_sph", "n_prim", "n_spairs", "n_ppairs", "qualifies", "rounds", "lanes", "max_rounds"),
+                        list(info)))
+
     def __del__(self):
         if getattr(self, "h", None):
             lib().smp_robot_destroy(self.h)
             self.h = None
+
+
+def _cover(status, c, r, n, what):
+    check(status, what)
+    return c[:n.value].copy(), r[:n.value].copy()
+
+
+def _pose12(pose):
+    if pose is None:
+        return None, None
+    p = np.ascontiguousarray(np.asarray(pose, np.float64).reshape(12))
+    return p, p.ctypes.data_as(_pd)
+
+
+def cover_box(half, pose=None, tol=0.01, max_spheres=16):
+    """smp_cover_box: (centres (m, 3), radii (m,)) of a conservative sphere cover of a box with half extents `half`,
+    on its longest axis; pose = 12 values (R row-major, then p) placing the box in the link's frame, None: identity."""
+    h = np.ascontiguousarray(np.asarray(half, np.float64).reshape(3))
+    keep, pp = _pose12(pose)
+    c, r, n = np.zeros((max(max_spheres, 1), 3)), np.zeros(max(max_spheres, 1)), ctypes.c_int()
+    return _cover(lib().smp_cover_box(h.ctypes.data_as(_pd), pp, float(tol), int(max_spheres), c.ctypes.data_as(_pd),
+                                      r.ctypes.data_as(_pd), ctypes.byref(n)), c, r, n, "smp_cover_box")
+
+
+def cover_cylinder(radius, half_length, pose=None, tol=0.01, max_spheres=16):
+    """smp_cover_cylinder: the same for a cylinder along its own z axis."""
+    keep, pp = _pose12(pose)
+    c, r, n = np.zeros((max(max_spheres, 1), 3)), np.zeros(max(max_spheres, 1)), ctypes.c_int()
+    return _cover(lib().smp_cover_cylinder(float(radius), float(half_length), pp, float(tol), int(max_spheres),
+                                           c.ctypes.data_as(_pd), r.ctypes.data_as(_pd), ctypes.byref(n)),
+                  c, r, n, "smp_cover_cylinder")
 
 
 class Scene:
@@ -179,6 +234,52 @@ class GpuPlanner:
               "smp_planner_create")
         self.h = h
         self.scene = None
+
+    def set_robot(self, robot):
+        """smp_planner_set_robot: swaps the planner's robot in place (Robot.attach after a grasp, the base robot after
+        the release); scene, disabled links, trees and query buffers stay."""
+        check(lib().smp_planner_set_robot(self.h, robot.h), "smp_planner_set_robot")
+        self.robot = robot
+
+    @staticmethod
+    def _carve(q, pad, links):
+        c = L.Carve()
+        for j in range(8):
+            c.q[j] = float(q[j])
+        c.pad = float(pad)
+        names = [n.encode() for n in (links or ())]
+        keep = (ctypes.c_char_p * max(len(names), 1))(*names)
+        c.links, c.n_links = keep, len(names)
+        return c, keep
+
+    def set_carve(self, q=None, pad=0.0, links=None):
+        """smp_planner_set_carve: the sticky self filter of set_scene_keys / _bt / _ot / _octomap_msg -- the robot's
+        volume at pose q (the pose the map was taken at), grown by pad metres, is carved out of the occupied keys inside
+        the device scene build.  links: the collision links to carve (None: all, attached objects included).
+        q=None turns it off.  set_scene and set_scene_device do not carve."""
+        if q is None:
+            check(lib().smp_planner_set_carve(self.h, None), "smp_planner_set_carve")
+            return
+        c, keep = self._carve(q, pad, links)
+        check(lib().smp_planner_set_carve(self.h, ctypes.byref(c)), "smp_planner_set_carve")
+
+    def carve_keys(self, keys, res, q, pad=0.0, links=None, z_offset=-0.02, floor_center=None, floor_distance=3.0):
+        """smp_carve_keys: one flag per key (1: carved by the self filter at q and pad), uint8 (n,).  The floor keys of
+        floor_center take part in the grid geometry only."""
+        keys = np.ascontiguousarray(np.asarray(keys).reshape(-1, 3), np.uint16)
+        o = Scene._opts(z_offset, floor_center, floor_distance)
+        o.resolution = res
+        c, keep = self._carve(q, pad, links)
+        out = np.zeros(len(keys), np.uint8)
+        check(lib().smp_carve_keys(self.h, keys.ctypes.data_as(ctypes.c_void_p), len(keys), ctypes.byref(o),
+                                   ctypes.byref(c), out.ctypes.data_as(ctypes.c_void_p), None), "smp_carve_keys")
+        return out
+
+    def last_carve(self):
+        """smp_planner_last_carve: n_carved, kernel_ms, total_ms of the last carving build or carve_keys call."""
+        info = L.CarveInfo()
+        check(lib().smp_planner_last_carve(self.h, ctypes.byref(info)), "smp_planner_last_carve")
+        return {f: getattr(info, f) for f, _ in L.CarveInfo._fields_}
 
     def set_scene(self, scene):
         check(lib().smp_planner_set_scene(self.h, scene.h), "smp_planner_set_scene")
@@ -676,6 +777,8 @@ class BiRRTstarPlanner:
         self.seed = seed
         self.query_id = 0
         self._gpu = None
+        self._detached = None  # the robot before attachObject, while an object is attached
+        self._self_filter = False
         self._env = [(0.0, 0.0), (0.0, 0.0)]
         self._start = self._goal = None
         self._flags = (True, True)
@@ -690,6 +793,15 @@ class BiRRTstarPlanner:
     def setOctree(self, octree, resolution=None, floor_center=None, floor_distance=3.0):
         """octree: .bt or .ot file bytes, or an (n, 3) array of occupied octomap keys (then `resolution` is
         required).  The first line tells the formats apart (AbstractOcTree::read / OcTree::readBinary)."""
+        if self._self_filter:
+            # the self filter lives in the device scene build (same arrays as the host path, carved)
+            if isinstance(octree, (bytes, bytearray)):
+                full = bytes(octree).startswith(b"# Octomap OcTree file")
+                (self._gpu.set_scene_ot if full else self._gpu.set_scene_bt)(octree, floor_center=floor_center,
+                                                                              floor_distance=floor_distance)
+            else:
+                self._gpu.set_scene_keys(octree, resolution, floor_center=floor_center, floor_distance=floor_distance)
+            return
         if isinstance(octree, (bytes, bytearray)):
             full = bytes(octree).startswith(b"# Octomap OcTree file")
             sc = (Scene.from_ot if full else Scene.from_bt)(octree, floor_center=floor_center,
@@ -700,6 +812,33 @@ class BiRRTstarPlanner:
 
     def setDisabledLinkMapCollisions(self, links):
         self._gpu.set_disabled_map_links(list(links))
+
+    def attachObject(self, link, centres, radii, name="attached_object", touch_links=()):
+        """Not in the reference (birrt_star.h:411-414 keeps attached objects as a stub): after a grasp, the object as
+        spheres in `link`'s frame becomes a collision link `name` of the planner's robot (Robot.attach, then
+        GpuPlanner.set_robot); every later check, plan and pass honours it.  Further objects stack."""
+        if not self._detached:
+            self._detached = self._gpu.robot
+        self._gpu.set_robot(self._gpu.robot.attach(link, centres, radii, name, touch_links))
+
+    def attachBox(self, link, half, pose=None, tol=0.01, name="attached_object", touch_links=(), max_spheres=16):
+        """Not in the reference: attachObject for a bounding box (half extents, placed in `link`'s frame by pose = R
+        row-major then p; None: centred on the frame), covered by cover_box within `tol`."""
+        centres, radii = cover_box(half, pose, tol, max_spheres)
+        self.attachObject(link, centres, radii, name, touch_links)
+
+    def setSelfFilter(self, pose_current=None, pad=0.0, links=None):
+        """Not in the reference: before each setOctree, the pose the octomap was taken at (poseCurrent).  The robot's
+        own voxels -- all collision links, or `links`, e.g. the grasped object's name -- grown by pad metres are then
+        carved out of the map inside setOctree.  pose_current=None turns the filter off."""
+        self._gpu.set_carve(pose_current, pad, links)
+        self._self_filter = pose_current is not None
+
+    def detachObject(self):
+        """Not in the reference: after the release, the robot as it was before the first attachObject."""
+        if self._detached:
+            self._gpu.set_robot(self._detached)
+            self._detached = None
 
     def setPlanningSceneInfo(self, size_x, size_y, scene_name="scenario"):
         self._env = [(float(size_x[0]), float(size_x[1])), (float(size_y[0]), float(size_y[1]))]
