@@ -536,7 +536,11 @@ int smp_repair_path(smp_planner* p, const double* waypoints, int64_t k, int chec
  * that it collides; map == 0 arises from a primitive overlapping a cell and means colliding.
  * An edge is the points 0..M of the density rule (smp_check_edges): map and self are the minima over its points,
  * map_point / self_point the lowest point index attaining each (map_point = -1 when map == D), and the link fields are
- * those of that point. */
+ * those of that point.
+ * Exactness of map against the true distance to the occupied cells: exact while every item centre is inside the grid,
+ * or max_dist + reach <= the pad (reach: the item's radius, or the radius of the ball about a primitive's centre that
+ * holds it; the pad: ceil(0.45 / res) + 2 cells around the occupied keys); otherwise an upper bound that may overstate,
+ * because an item centred outside the grid gives D whatever its distance.  self has no such limit. */
 typedef struct smp_clearance { double map, self; int32_t map_link, self_a, self_b, pad; } smp_clearance;            /* 32 B */
 typedef struct smp_edge_clearance { double map, self; int32_t map_point, self_point, map_link, self_a, self_b, n_points; } smp_edge_clearance;  /* 40 B */
 typedef struct smp_clearance_info { int64_t n_points; double kernel_ms, total_ms; } smp_clearance_info;             /* may be NULL */
@@ -568,6 +572,9 @@ int smp_clearance_edges(smp_planner* p, const double* from_rows, const double* t
  * and sqrt(fl(r * r)) == r) 2 and 3 imply 1 for a part whose margin is positive, so the kernel skips the boolean test of
  * that part; the tests compare against the conjunction.
  * An edge is clear iff all points 0..M of the density rule are; first_invalid is the lowest point that is not clear.
+ * Exactness of the map part against the true distance to the occupied cells: exact while every item centre is inside
+ * the grid, or margin + reach <= the pad (as under "Clearance queries"); otherwise an upper bound that may overstate:
+ * an item centred outside the grid is clear whatever its distance.  The boolean checks are exact everywhere.
  * SMP_ERR_ARG: a margin that is not finite or is negative; a map margin whose largest prefilter threshold
  * floor(((r + mm + 1e-6) / res)^2) reaches the clamp of the box-gap field (the rule of smp_clearance_* for max_dist); a
  * positive map margin with check_map and no scene.  A NULL margin or {0, 0} gives results identical to the plain entry
