@@ -134,33 +134,28 @@ class BiRRTstarPlanner {
                    int planner_run_number = 0) {
     (void)search_space; (void)show_tree_vis; (void)iter_sleep; (void)planner_run_number;
     if (!ready_) return false;
-    smp_query q;
-    std::memset(&q, 0, sizeof(q));
-    for (int j = 0; j < 8; ++j) { q.start[j] = start_[j]; q.goal[j] = goal_[j]; }
-    q.env_x[0] = env_x_[0]; q.env_x[1] = env_x_[1];
-    q.env_y[0] = env_y_[0]; q.env_y[1] = env_y_[1];
-    q.check_self = self_;
-    q.check_map = map_;
-    q.budget_kind = flag_iter_or_time ? SMP_BUDGET_SECONDS : SMP_BUDGET_ITERATIONS;
-    q.budget = max_iter_time;
-    q.seed = seed_++;
-    q.query_id = 0;
+    const smp_query q = next_query(flag_iter_or_time, max_iter_time);
     smp_result r;
     std::memset(&r, 0, sizeof(r));
-    int st = smp_plan(planner_, &q, &r);
-    traj_.clear();
-    if (st == SMP_OK) {
-      traj_.resize((size_t)r.n_waypoints, vector<double>(8));
-      for (int64_t i = 0; i < r.n_waypoints; ++i)
-        for (int j = 0; j < 8; ++j) traj_[(size_t)i][(size_t)j] = r.waypoints[i * 8 + j];
-    }
-    stats_ = r.stats;
-    smp_result_free(&r);
-    if (st == SMP_OK) return true;
-    if (st == SMP_ERR_NO_SOLUTION || st == SMP_ERR_START_INVALID || st == SMP_ERR_GOAL_INVALID) return false;
-    check(st, "smp_plan");
-    return false;
+    return planned(smp_plan(planner_, &q, &r), &r, "smp_plan");
   }
+
+  // Not in the reference, where the branch is dead (squirrel_8dof_planner.cpp:505-508, 595-598 print "COMBINED 2DOF AND
+  // 8DOF PLANNING NOT IMPLEMENTED!"): run_planner for a goal across the room, the node's two-stage plan
+  // (squirrel_8dof_planner.h:50) -- a base route with the arm held at opts.arm (pose_folded_arm) over the environment
+  // of setPlanningSceneInfo, kept opts.map_margin (astar_safety_distance) from the map and checked densely, then the
+  // 8-DoF planner for the last opts.handover_distance (distance_birrt_star_planning) metres (smp_plan_far).  The
+  // trajectory is the base stage's rows followed by the plan's; lastFar() tells them apart (n_route_rows) and says
+  // where a failed call ended (stage).  False, no trajectory, as run_planner.
+  bool run_planner_far(bool flag_iter_or_time, double max_iter_time, const smp_far_opts& opts) {
+    if (!ready_) return false;
+    const smp_query q = next_query(flag_iter_or_time, max_iter_time);
+    smp_result r;
+    std::memset(&r, 0, sizeof(r));
+    return planned(smp_plan_far(planner_, &q, &opts, &r, &far_), &r, "smp_plan_far");
+  }
+  // Stages, counts and timing of the last run_planner_far.
+  const smp_far_info& lastFar() const { return far_; }
 
   void reset_planner_and_config() {
     reset_planner_only();
@@ -631,6 +626,36 @@ class BiRRTstarPlanner {
   void need() const {
     if (!planner_) throw std::runtime_error("smp: BiRRTstarPlanner::initialize() not called");
   }
+  // The query of the next planning call from init_planner's and setPlanningSceneInfo's values.
+  smp_query next_query(bool flag_iter_or_time, double max_iter_time) {
+    smp_query q;
+    std::memset(&q, 0, sizeof(q));
+    for (int j = 0; j < 8; ++j) { q.start[j] = start_[j]; q.goal[j] = goal_[j]; }
+    q.env_x[0] = env_x_[0]; q.env_x[1] = env_x_[1];
+    q.env_y[0] = env_y_[0]; q.env_y[1] = env_y_[1];
+    q.check_self = self_;
+    q.check_map = map_;
+    q.budget_kind = flag_iter_or_time ? SMP_BUDGET_SECONDS : SMP_BUDGET_ITERATIONS;
+    q.budget = max_iter_time;
+    q.seed = seed_++;
+    q.query_id = 0;
+    return q;
+  }
+  // What a planning call leaves behind: the trajectory of a success, the statistics, run_planner's return value.
+  bool planned(int st, smp_result* r, const char* what) {
+    traj_.clear();
+    if (st == SMP_OK) {
+      traj_.resize((size_t)r->n_waypoints, vector<double>(8));
+      for (int64_t i = 0; i < r->n_waypoints; ++i)
+        for (int j = 0; j < 8; ++j) traj_[(size_t)i][(size_t)j] = r->waypoints[i * 8 + j];
+    }
+    stats_ = r->stats;
+    smp_result_free(r);
+    if (st == SMP_OK) return true;
+    if (st == SMP_ERR_NO_SOLUTION || st == SMP_ERR_START_INVALID || st == SMP_ERR_GOAL_INVALID) return false;
+    check(st, what);
+    return false;
+  }
   std::string link_name(int l) const { return l >= 0 ? std::string(smp_robot_link_name(robot_, l)) : std::string(); }
   void set_flag(int smp_params::*field, int v) {
     params_.*field = v;
@@ -653,6 +678,7 @@ class BiRRTstarPlanner {
   smp_stats stats_{};
   smp_shortcut_info shortcut_{};
   smp_repair_info repair_{};
+  smp_far_info far_{};
   double env_x_[2] = {0, 0}, env_y_[2] = {0, 0};
   vector<double> start_, goal_;
   bool self_ = true, map_ = true, ready_ = false;
@@ -798,6 +824,28 @@ class MultiGpuPlanner {
   smp_robot* robot_ = nullptr;
   std::vector<smp_planner*> planners_;
 };
+
+// The node's two-stage plan (squirrel_8dof_planner.h:50; dead in the reference, squirrel_8dof_planner.cpp:505-508,
+// 595-598) from the node's own parameters (parameters.yaml): pose_folded_arm, astar_safety_distance and
+// distance_birrt_star_planning become smp_far_opts' arm, map_margin and handover_distance; the lattice stays at its
+// defaults (0.1 m, 8 headings) unless pitch / n_theta say otherwise.  Call it where the node calls run_planner, after
+// init_planner; the trajectory is planner.getJointTrajectoryRef(), info (may be NULL) receives planner.lastFar().
+inline bool planFar(birrt_star_motion_planning::BiRRTstarPlanner& planner, bool flag_iter_or_time, double max_iter_time,
+                    const std::vector<double>& pose_folded_arm, double astar_safety_distance,
+                    double distance_birrt_star_planning, smp_far_info* info = nullptr, double pitch = 0.0,
+                    int n_theta = 0) {
+  if (pose_folded_arm.size() != 5) throw std::runtime_error("smp: planFar: pose_folded_arm has 5 joints");
+  smp_far_opts o;
+  smp_far_opts_default(&o);
+  for (int j = 0; j < 5; ++j) o.arm[j] = pose_folded_arm[(size_t)j];
+  o.map_margin = astar_safety_distance;
+  o.handover_distance = distance_birrt_star_planning;
+  if (pitch > 0.0) o.pitch = pitch;
+  if (n_theta > 0) o.n_theta = n_theta;
+  const bool ok = planner.run_planner_far(flag_iter_or_time, max_iter_time, o);
+  if (info) *info = planner.lastFar();
+  return ok;
+}
 
 // Planner::normalizeTrajectory (squirrel_8dof_planner.cpp:1557-1637), same signature and the same behaviour: the
 // output is left untouched for an empty normalized pose, a single pose or a dimension mismatch.  Host only.

@@ -59,6 +59,14 @@
  *                              contacts only once they exist)
  *   smp_clearance_edges        the same along dense edges of the density rule: each edge's minima, the points and the
  *                              links attaining them, one launch (the reference has no counterpart)
+ *   smp_base_free_map          the first stage of the node's two-stage planner (squirrel_8dof_planner.h:50), a 2-D base
+ *   smp_base_route             path with the arm folded and 8 DoF only for the last distance_birrt_star_planning metres.
+ *   smp_plan_far               In the reference that branch is dead: both service callbacks print "COMBINED 2DOF AND
+ *                              8DOF PLANNING NOT IMPLEMENTED!" and return false (squirrel_8dof_planner.cpp:505-508,
+ *                              595-598).  Here: the base's free space as a slice of C-space, every lattice node
+ *                              (x, y, theta, folded arm) answered by the real checker in one launch; a Dijkstra route
+ *                              over the bit grid on the host; the route checked densely, then smp_plan for the tail
+ *                              (the pop-back loop of squirrel_8dof_planner.cpp:1209-1215 chooses the handover)
  *   smp_normalize_trajectory   Planner::normalizeTrajectory (squirrel_8dof_planner.cpp:1557-1637), host only
  *   smp_ik_solve               BiRRTstarPlanner::getFullPoseFromEEPose (birrt_star.cpp:1627-1686) ->
  *                              RobotController::run_VDLS_Control_Connector (control_laws.cpp:3283-3712):
@@ -598,6 +606,92 @@ int smp_shortcut_path_margin(smp_planner* p, const double* waypoints, int64_t k,
 int smp_repair_path_margin(smp_planner* p, const double* waypoints, int64_t k, int check_self, int check_map,
                            const smp_repair_opts* opts, const smp_margin* margin, double** out_waypoints,
                            int64_t* n_out, smp_repair_info* info);
+
+/* Far goals: the base lattice, the route over it and the staged plan (the reference's two-stage planner,
+ * squirrel_8dof_planner.h:50, whose branch is dead there: squirrel_8dof_planner.cpp:505-508, 595-598).
+ *
+ * The lattice.  Node (ix, iy, t) is the configuration [x0 + ix * pitch, y0 + iy * pitch, theta0 + t * dtheta, arm[0..4]]:
+ * the integer converted to double, then the product, then the sum, each rounded on its own (formed on the device; no
+ * table of configurations is uploaded).  Node number n = (t * ny + iy) * nx + ix, N = nx * ny * n_theta.
+ * smp_base_lattice_fit (host only): x0 = env_x[0], nx = (int)floor((env_x[1] - env_x[0]) / pitch) + 1, y likewise,
+ * dtheta = (2.0 * M_PI) / n_theta, wrap_theta = 1.  SMP_ERR_ARG: a NULL argument, a non-finite value, pitch <= 0,
+ * n_theta < 1, a reversed interval; SMP_ERR_CAPACITY: more than SMP_LATTICE_MAX_NODES nodes.
+ *
+ * smp_base_free_map.  Bit n % 32 of word n / 32 of free_bits (ceil(N / 32) words; the unused bits of the last word are
+ * 0) is 1 iff smp_check_configs(q_n, check_self = 0, check_map = 1) says valid, or, with margin->map > 0, iff
+ * smp_check_configs_margin(q_n, 0, 1, {margin->map, 0}) says clear (margin->self is ignored; NULL means no margin) --
+ * bit for bit those calls' answers: the same tile on the same values, the disabled links of smp_set_disabled_map_links
+ * honoured, an item centred outside the grid free.  The arm's self test is not part of the map: the route's dense
+ * check in smp_plan_far carries it.  One launch, one workgroup per 32 consecutive nodes, each storing its own word.
+ * SMP_ERR_ARG: a NULL planner, lattice or output, a non-finite field, pitch <= 0, a count < 1, no scene, a margin that
+ * smp_check_configs_margin refuses.  SMP_ERR_CAPACITY: N > SMP_LATTICE_MAX_NODES. */
+enum { SMP_LATTICE_MAX_NODES = 1 << 26 };
+typedef struct smp_base_lattice {
+  double x0, y0, pitch;     /* node (ix, iy): x = x0 + ix * pitch, y = y0 + iy * pitch; pitch finite, > 0 */
+  int nx, ny;               /* >= 1 */
+  double theta0, dtheta;    /* heading t: theta0 + t * dtheta */
+  int n_theta;              /* >= 1 */
+  int wrap_theta;           /* 1: headings 0 and n_theta - 1 are neighbours (a full circle) */
+  double arm[5];            /* arm joints held on the lattice (pose_folded_arm) */
+} smp_base_lattice;
+typedef struct smp_base_map_info { int64_t n_nodes, n_free; double kernel_ms, total_ms; } smp_base_map_info; /* may be NULL */
+int smp_base_lattice_fit(const double env_x[2], const double env_y[2], double pitch, int n_theta, double theta0,
+                         const double arm[5], smp_base_lattice* out);
+int smp_base_free_map(smp_planner* p, const smp_base_lattice* lat, const smp_margin* margin, uint32_t* free_bits,
+                      smp_base_map_info* info);
+
+/* smp_base_route (host only): the cheapest route over the free nodes of a lattice.
+ *  Snapping of from / to (x, y, theta): ix = (int)floor((x - x0) / pitch + 0.5), iy likewise,
+ *   t = (int)floor((theta - theta0) / dtheta + 0.5), taken modulo n_theta with wrap_theta; an index outside the lattice:
+ *   SMP_ERR_ARG.  A blocked node is replaced from the square rings r = 1 .. snap_cells of its heading layer, ascending:
+ *   within a ring the free node with the least (ix - ix0)^2 + (iy - iy0)^2, ties to the smaller node number.  None:
+ *   SMP_ERR_START_INVALID for from, SMP_ERR_GOAL_INVALID for to.
+ *  Graph: the 4 axis steps (weight pitch); the 4 diagonal steps (weight sqrt(pitch * pitch + pitch * pitch)) only where
+ *   both axis cells between the two nodes are free in that layer; the heading steps t - 1, t + 1 at the same (ix, iy)
+ *   (weight fabs(dtheta)), wrapping iff wrap_theta and n_theta > 1 -- the reference's dist with weights 1.
+ *  Search: Dijkstra.  The priority is the pair (cost, node number), ascending; a node is settled at its first pop;
+ *   dp starts at +inf and is relaxed with dp[u] + w < dp[v], strict; neighbours are tried in the order -y, -x, +x, +y,
+ *   (-x,-y), (+x,-y), (-x,+y), (+x,+y), t - 1, t + 1.  The search stops when to_node is settled; to_node never
+ *   settled: SMP_ERR_NO_SOLUTION (from_node, to_node and n_settled are still reported).
+ *  Output: *out_chain (n_chain x 3: ix, iy, t; may be NULL) holds every node from from_node to to_node; *out_rows
+ *   (n_out x 8) the chain with runs of equal step (dix, diy, dt) merged -- a node is kept where the step changes, plus
+ *   both ends -- each row the node's configuration as above; from_node == to_node gives one row.  Both are released
+ *   with smp_buffer_free. */
+typedef struct smp_route_info { int32_t from_node[3], to_node[3]; int64_t n_chain, n_settled; double cost; } smp_route_info;
+int smp_base_route(const smp_base_lattice* lat, const uint32_t* free_bits, const double from[3], const double to[3],
+                   int snap_cells, double** out_rows, int64_t* n_out, int32_t** out_chain, smp_route_info* info);
+
+/* smp_plan_far: the staged call.
+ *  1. The lattice smp_base_lattice_fit(q->env_x, q->env_y, pitch, n_theta, 0, arm) and its free map at the margin
+ *     {map_margin, 0}.  An unconfined query (env_x or env_y of (0, 0)): SMP_ERR_ARG.
+ *  2. smp_base_route from q->start[0..2] to q->goal[0..2].
+ *  3. Handover: with the chain c_0 .. c_m, acc = 0 and j = m; while j > 0 and acc < handover_distance, the planar length
+ *     of the step c_j -> c_j-1 (pitch, the diagonal weight, or 0 for a heading step) is added to acc and j decremented
+ *     (squirrel_8dof_planner.cpp:1209-1215).  j == 0: no base stage, the call is smp_plan(p, q, out), n_route_rows = 0.
+ *  4. The route rows -- q->start, then the merged rows of the chain c_0 .. c_j -- validated and shortened in one
+ *     smp_shortcut_path_margin call with the query's check_self / check_map, the margin {map_margin, 0} and `window`
+ *     (the first edge folds the arm if the caller has not).  Blocked: SMP_ERR_NO_SOLUTION, stage 3, check.first_blocked.
+ *  5. smp_plan on q with start replaced by the last row of step 4's output, bit for bit.  out is that call's result with
+ *     its waypoints prefixed by step 4's rows (the plan's own first row, equal to the last route row, dropped); stats
+ *     and cost_rows are the tail's.  A failing tail returns its status with stage 4; out->waypoints then holds the route
+ *     rows alone. */
+typedef struct smp_far_opts {
+  double pitch; int n_theta; double arm[5];
+  double handover_distance;   /* distance_birrt_star_planning: metres of base route left to the 8-DoF planner */
+  double map_margin;          /* astar_safety_distance's role: margin of the free map and of the route's dense check; 0: boolean */
+  int window;                 /* smp_shortcut_path's window over the route rows; <= 0: all pairs */
+  int snap_cells;
+} smp_far_opts;
+void smp_far_opts_default(smp_far_opts*);
+    /* pitch 0.1, n_theta 8, arm = pose_folded_arm, handover 2.0, margin 0, window 0, snap 2 */
+typedef struct smp_far_info {
+  int stage;                  /* where the call ended: 0 complete, 1 free map, 2 route search, 3 route check, 4 tail plan */
+  smp_base_map_info map; smp_route_info route; int32_t handover_node[3];
+  int64_t n_route_rows;       /* leading rows of out->waypoints that belong to the base stage; 0: planned directly */
+  smp_shortcut_info check;    /* the route's dense check */
+  double route_ms, total_ms;  /* host clock */
+} smp_far_info;
+int smp_plan_far(smp_planner* p, const smp_query* q, const smp_far_opts* o, smp_result* out, smp_far_info* info);
 
 /* n poses of `dim` values, row-major.  *n_out = rows of the normalized trajectory; with out == NULL only counts,
  * else writes them (SMP_ERR_CAPACITY if out_cap < *n_out).  For dim < 1 or n <= 1 the reference leaves its output

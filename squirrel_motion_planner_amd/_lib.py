@@ -157,6 +157,36 @@ class ClearanceInfo(ctypes.Structure):
     _fields_ = [("n_points", _i64), ("kernel_ms", _d), ("total_ms", _d)]
 
 
+class BaseLattice(ctypes.Structure):
+    """smp_base_lattice: the base's lattice (x, y, heading) with the arm joints held on it."""
+    _fields_ = [("x0", _d), ("y0", _d), ("pitch", _d), ("nx", _i), ("ny", _i), ("theta0", _d), ("dtheta", _d),
+                ("n_theta", _i), ("wrap_theta", _i), ("arm", _d * 5)]
+
+
+class BaseMapInfo(ctypes.Structure):
+    """smp_base_map_info: nodes, free nodes and timing of one smp_base_free_map call."""
+    _fields_ = [("n_nodes", _i64), ("n_free", _i64), ("kernel_ms", _d), ("total_ms", _d)]
+
+
+class RouteInfo(ctypes.Structure):
+    """smp_route_info: the snapped end nodes (ix, iy, t), chain length, settled nodes and cost of one route search."""
+    _fields_ = [("from_node", ctypes.c_int32 * 3), ("to_node", ctypes.c_int32 * 3), ("n_chain", _i64),
+                ("n_settled", _i64), ("cost", _d)]
+
+
+class FarOpts(ctypes.Structure):
+    """smp_far_opts: lattice, handover distance, map margin, shortcut window and snapping of smp_plan_far."""
+    _fields_ = [("pitch", _d), ("n_theta", _i), ("arm", _d * 5), ("handover_distance", _d), ("map_margin", _d),
+                ("window", _i), ("snap_cells", _i)]
+
+
+class FarInfo(ctypes.Structure):
+    """smp_far_info: where smp_plan_far ended and what its stages reported."""
+    _fields_ = [("stage", _i), ("map", BaseMapInfo), ("route", RouteInfo), ("handover_node", ctypes.c_int32 * 3),
+                ("n_route_rows", _i64), ("check", ShortcutInfo), ("route_ms", _d), ("total_ms", _d)]
+
+
+SMP_LATTICE_MAX_NODES = 1 << 26
 SMP_EDGE_MAX_POINTS = 1 << 20
 SMP_EDGE_TABLE_MAX = 1 << 20
 
@@ -233,6 +263,14 @@ EXPORTS = [
                                       ctypes.POINTER(_i64), ctypes.POINTER(ShortcutInfo)]),
     ("smp_repair_path_margin", _i, [_p, _pd, _i64, _i, _i, ctypes.POINTER(RepairOpts), ctypes.POINTER(Margin),
                                     ctypes.POINTER(_pd), ctypes.POINTER(_i64), ctypes.POINTER(RepairInfo)]),
+    ("smp_base_lattice_fit", _i, [_pd, _pd, _d, _i, _d, _pd, ctypes.POINTER(BaseLattice)]),
+    ("smp_base_free_map", _i, [_p, ctypes.POINTER(BaseLattice), ctypes.POINTER(Margin), _p,
+                               ctypes.POINTER(BaseMapInfo)]),
+    ("smp_base_route", _i, [ctypes.POINTER(BaseLattice), _p, _pd, _pd, _i, ctypes.POINTER(_pd), ctypes.POINTER(_i64),
+                            ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), ctypes.POINTER(RouteInfo)]),
+    ("smp_far_opts_default", None, [ctypes.POINTER(FarOpts)]),
+    ("smp_plan_far", _i, [_p, ctypes.POINTER(Query), ctypes.POINTER(FarOpts), ctypes.POINTER(Result),
+                          ctypes.POINTER(FarInfo)]),
     ("smp_normalize_trajectory", _i, [_pd, _i64, _i, _pd, _pd, _i64, ctypes.POINTER(_i64)]),
     ("smp_ik_solve", _i, [_p, ctypes.POINTER(IkRequest), _i, ctypes.POINTER(IkResult)]),
     ("smp_find_goal_pose", _i, [_p, _pd, _pd, _d, _i, _i, _pd, ctypes.POINTER(_i), ctypes.POINTER(GoalSearch)]),

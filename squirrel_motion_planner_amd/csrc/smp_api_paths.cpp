@@ -1,6 +1,6 @@
 // C ABI implementation (include/smp_gpu.h), path tools: batched dense edge checks, shortcutting, one-via detours and
-// path repair, clearance queries and the margin variants of the passes (kernels: smp_edges.hip, smp_repair.hip,
-// smp_clearance.hip, smp_margin.hip).  Every entry point validates, builds its tables, launches (run_pass),
+// path repair, clearance queries, the margin variants of the passes and the base's free map (kernels: smp_edges.hip,
+// smp_repair.hip, smp_clearance.hip, smp_margin.hip, smp_lattice.hip).  Every entry point validates, builds its tables, launches (run_pass),
 // post-processes and fills its info record; the plain logic between the launches is smp_paths.cpp's.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 
 #include "smp_paths.h"
 #include "smp_planner.h"
+#include "smp_route.h"
 
 using namespace smp;
 
@@ -456,6 +457,44 @@ int smp_repair_path_margin(smp_planner* p, const double* waypoints, int64_t k, i
 }
 
 void smp_buffer_free(void* buffer) { std::free(buffer); }
+
+// ------------------------------------------------------------------------------------------ the base's free map
+// One launch over the tiles of the lattice's nodes; the kernels form the configurations themselves, so the call uploads
+// nothing but its arguments, and the words it downloads are the caller's bit grid.
+int smp_base_free_map(smp_planner* p, const smp_base_lattice* lat, const smp_margin* margin, uint32_t* free_bits,
+                      smp_base_map_info* info) {
+  if (!p || !lat || !free_bits) return SMP_ERR_ARG;
+  const auto t_begin = std::chrono::steady_clock::now();
+  if (info) std::memset(info, 0, sizeof(*info));
+  if (int b_ = busy_check(p)) return b_;
+  LatticeDev ld;
+  if (int st = lattice_dev(lat, &ld)) return st;
+  const smp_margin map_only{margin ? margin->map : 0.0, 0.0};
+  MarginCfg mg;
+  bool on;
+  if (int st = margin_cfg(p, &map_only, 0, 1, &mg, &on)) return st;
+  if (!p->have_scene) return SMP_ERR_ARG;
+  const int n_items = (int)((ld.n + PASS_CT - 1) / PASS_CT);
+  double ms = 0;
+  const int st = run_pass(
+      p, (size_t)n_items, [] { return (int)SMP_OK; },
+      [&](int grid) {
+        if (on)
+          launch_margin_base_map(grid, p->stream, p->d_rb, p->sc, p->d_mc, mg, ld, n_items, p->d_ecounter.p,
+                                 p->d_lbits.p);
+        else
+          launch_base_map(grid, p->stream, p->d_rb, p->sc, p->d_mc, ld, n_items, p->d_ecounter.p, p->d_lbits.p);
+      },
+      p->d_lbits, free_bits, (size_t)n_items, &ms);
+  if (st != SMP_OK) return st;
+  p->last_check_ms = ms;
+  if (info) {
+    info->n_nodes = ld.n;
+    for (int i = 0; i < n_items; ++i) info->n_free += __builtin_popcount(free_bits[i]);
+    fill_times(info, ms, t_begin);
+  }
+  return SMP_OK;
+}
 
 // ------------------------------------------------------------------------------------------ clearance queries
 static_assert(sizeof(smp_clearance) == sizeof(ClearDev) && sizeof(smp_edge_clearance) == sizeof(EdgeClearDev),

@@ -30,11 +30,14 @@ struct MarginCfg {
 // order and their results are those of the plain passes with "colliding" read as "not clear":
 //   configs: item t is the tile of configurations 32 t .. min(32 t + 31, n - 1) of q_rows (row-major n x 8),
 //            clear[i] = 1 iff configuration i is clear;
+//   base map: launch_base_map's tiles of lattice nodes (smp_pass.h), bit c of bits[t] set iff node 32 t + c is clear;
 //   edges:   launch_edges' tables, first_invalid[e] = the lowest point of edge e that is not clear, -1 if none;
 //   detours: launch_detours' tables and record, free = every point of both legs is clear.
 void launch_margin_configs(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc,
                            const MarginCfg& cfg, const double* q_rows, long long n, int n_items, unsigned* counter,
                            uint8_t* clear);
+void launch_margin_base_map(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc,
+                            const MarginCfg& cfg, LatticeDev lat, int n_items, unsigned* counter, uint32_t* bits);
 void launch_margin_edges(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc,
                          const MarginCfg& cfg, const EdgeDev* edges, const int* order, int n, unsigned* counter,
                          int* first_invalid);

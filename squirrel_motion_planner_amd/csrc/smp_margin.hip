@@ -406,6 +406,30 @@ __global__ void __launch_bounds__(BLOCK) margin_configs_kernel(const RobotDev* _
       });
 }
 
+// The base's free map at a map margin (base_map_kernel's tiles, smp_lattice.hip): item t is the tile of lattice nodes
+// 32 t .. and bits[t] its word, bit c set iff node 32 t + c is clear.  cfg asks for the map part alone.
+__global__ void __launch_bounds__(BLOCK) margin_base_map_kernel(const RobotDev* __restrict__ rb, SceneDev sc_in,
+                                                                const MapCfg* __restrict__ mc, MarginCfg cfg,
+                                                                LatticeDev lat, int n_items,
+                                                                unsigned* __restrict__ counter,
+                                                                uint32_t* __restrict__ bits) {
+  SMP_MARGIN_PROLOGUE();
+  (void)tid;  // (lattice_tile and tile_mask index by thread themselves)
+  ticket_loop(
+      counter, (unsigned)n_items,
+      [&](unsigned slot) {
+        const long long n0 = (long long)slot * PASS_CT;
+        const int nc = __builtin_amdgcn_readfirstlane((int)min((long long)PASS_CT, lat.n - n0));
+        lattice_tile(ql, lat, n0, nc);
+        __syncthreads();
+        margin_tile(&s_rb, sc_in, sc, &s_mc, cfg, nc, ql, L);  // (ends with a barrier)
+        const unsigned long long mask = tile_mask(L, nc);
+        __syncthreads();  // ql and the flags are rewritten by the next tile
+        return lattice_word(mask, nc);
+      },
+      [&](unsigned slot, uint32_t word) { bits[slot] = word; });
+}
+
 // Dense edges (edges_kernel's walk): the first tile that holds a point that is not clear ends the edge.
 __global__ void __launch_bounds__(BLOCK) margin_edges_kernel(const RobotDev* __restrict__ rb, SceneDev sc_in,
                                                              const MapCfg* __restrict__ mc, MarginCfg cfg,
@@ -520,7 +544,7 @@ __global__ void __launch_bounds__(BLOCK) margin_detours_kernel(const RobotDev* _
 }
 
 size_t margin_kernels_private_bytes() {
-  return std::max(kernel_private_bytes(&margin_configs_kernel),
+  return std::max(std::max(kernel_private_bytes(&margin_configs_kernel), kernel_private_bytes(&margin_base_map_kernel)),
                   std::max(kernel_private_bytes(&margin_edges_kernel), kernel_private_bytes(&margin_detours_kernel)));
 }
 
@@ -529,6 +553,12 @@ void launch_margin_configs(int grid, hipStream_t st, const RobotDev* rb, SceneDe
                            uint8_t* clear) {
   hipLaunchKernelGGL(margin_configs_kernel, dim3(grid), dim3(BLOCK), 0, st, rb, sc, mc, cfg, q_rows, n, n_items, counter,
                      clear);
+}
+
+void launch_margin_base_map(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc,
+                            const MarginCfg& cfg, LatticeDev lat, int n_items, unsigned* counter, uint32_t* bits) {
+  hipLaunchKernelGGL(margin_base_map_kernel, dim3(grid), dim3(BLOCK), 0, st, rb, sc, mc, cfg, lat, n_items, counter,
+                     bits);
 }
 
 void launch_margin_edges(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc,

@@ -44,7 +44,31 @@ SMP_HD int edge_segments(double sr, double sp, double step, int n_seg, int max_p
   return n_seg * (x < 1.0 ? 1 : (int)x);
 }
 
+// The base lattice as the free-map kernels see it (smp_base_lattice, include/smp_gpu.h "Far goals"): node
+// n = (t * ny + iy) * nx + ix is the configuration [x0 + ix * pitch, y0 + iy * pitch, theta0 + t * dtheta, arm].
+struct LatticeDev {
+  double x0, y0, pitch, theta0, dtheta;
+  double arm[NJ - 3];
+  int nx, ny;
+  long long n;  // nx * ny * n_theta
+};
+
+// Coordinate j of node (ix, iy, t): the integer converted, then the product, then the sum, each rounded on its own
+// (no contraction, on host and device alike: smp_route.cpp forms the route's rows with it).
+SMP_HD double lattice_coord(const LatticeDev& lat, int ix, int iy, int t, int j) {
+  if (j == 0) return lat.x0 + (double)ix * lat.pitch;
+  if (j == 1) return lat.y0 + (double)iy * lat.pitch;
+  if (j == 2) return lat.theta0 + (double)t * lat.dtheta;
+  return j == 3 ? lat.arm[0] : j == 4 ? lat.arm[1] : j == 5 ? lat.arm[2] : j == 6 ? lat.arm[3] : lat.arm[4];
+}
+
 #if defined(__HIPCC__)
+
+// The launch of base_map_kernel (smp_lattice.hip; the margin variant is smp_margin.h's): item t is the tile of nodes
+// 32 t .. min(32 t + 31, n - 1), bits[t] its word -- bit c set iff node 32 t + c is free of the map.
+void launch_base_map(int grid, hipStream_t st, const RobotDev* rb, SceneDev sc, const MapCfg* mc, LatticeDev lat,
+                     int n_items, unsigned* counter, uint32_t* bits);
+size_t lattice_kernels_private_bytes();
 
 // The launches of edges_kernel (smp_edges.hip) and detours_kernel (smp_repair.hip); clearance_kernel's is in
 // smp_clearance.h.  Workgroups draw their items from *counter, zeroed on the stream before the launch.
@@ -121,6 +145,23 @@ __device__ __forceinline__ void edge_tile(double (*ql)[NJ], const double* ea, co
     const int c = it / NJ, j = it - c * NJ;
     ql[c][j] = ea[j] + (double)(base + c) * es[j];
   }
+}
+
+// Nodes n0 .. n0 + nc - 1 of the lattice into the tile, a coordinate per thread (nc <= PASS_CT, one trip).
+__device__ __forceinline__ void lattice_tile(double (*ql)[NJ], const LatticeDev& lat, long long n0, int nc) {
+  static_assert(PASS_CT * NJ <= BLOCK, "a thread per coordinate of the tile");
+  const int it = threadIdx.x;
+  if (it < nc * NJ) {
+    const int c = it / NJ, j = it - c * NJ;
+    const long long n = n0 + c, row = n / lat.nx;
+    ql[c][j] = lattice_coord(lat, (int)(n - row * lat.nx), (int)(row % lat.ny), (int)(row / lat.ny), j);
+  }
+}
+
+// A free-map tile's word from the mask of its blocked configurations: bit c set iff c < nc and configuration c is free.
+__device__ __forceinline__ uint32_t lattice_word(unsigned long long blocked, int nc) {
+  const uint32_t all = nc >= 32 ? 0xffffffffu : ((1u << nc) - 1u);
+  return ~(uint32_t)blocked & all;
 }
 
 #endif  // __HIPCC__

@@ -128,6 +128,8 @@ struct smp_planner {
   // margin checks (smp_check_configs_margin): per-configuration results; the rows are d_clq, the other tables those of
   // the plain passes
   smp::DBuf<uint8_t> d_mclear;
+  // the base's free map (smp_base_free_map): one word per tile of 32 lattice nodes; the work counter is d_ecounter
+  smp::DBuf<uint32_t> d_lbits;
   // self filter (smp_planner_set_carve / smp_carve_keys): the sticky carve of the device scene builds, its links by
   // name (resolved against the robot at every build), and the carve launches' scratch: the world items, the flags of
   // the standalone call, the carved-key count; ev2 / ev3 time the carve launches inside a build

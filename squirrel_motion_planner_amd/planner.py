@@ -460,6 +460,53 @@ class GpuPlanner:
         rc = lib().smp_repair_path_margin(*head, _margin(margin), *tail)
         return _returned_path("smp_repair_path_margin", rc, out, n_out, info)
 
+    def base_free_map(self, lattice, margin=None):
+        """smp_base_free_map: the base's free space on `lattice` (base_lattice_fit's, or a dict of smp_base_lattice's
+        fields) with the arm held at lattice.arm, every node answered by the map check in one launch.  Returns
+        (free (n_theta, ny, nx) bool, info dict); margin: a map margin in metres (or a (map, self) pair, whose self part
+        is ignored), None: the boolean check."""
+        lat = _lattice(lattice)
+        n = max(lat.nx, 0) * max(lat.ny, 0) * max(lat.n_theta, 0)
+        bits = np.zeros(max((n + 31) // 32, 1) if n <= L.SMP_LATTICE_MAX_NODES else 1, np.uint32)
+        info = L.BaseMapInfo()
+        m = None if margin is None else _margin(margin if np.ndim(margin) else (margin, 0.0))
+        check(lib().smp_base_free_map(self.h, ctypes.byref(lat), m, bits.ctypes.data_as(ctypes.c_void_p),
+                                      ctypes.byref(info)), "smp_base_free_map")
+        free = np.unpackbits(bits.view(np.uint8), bitorder="little")[:n].astype(bool)
+        self.base_map_bits = bits  # the words as the call left them (the unused bits of the last one are 0)
+        return free.reshape(lat.n_theta, lat.ny, lat.nx), {f: getattr(info, f) for f, _ in L.BaseMapInfo._fields_}
+
+    @staticmethod
+    def base_route(lattice, free, frm, to, snap_cells=2):
+        """smp_base_route over a free map of base_free_map: the module's base_route (host only)."""
+        return base_route(lattice, free, frm, to, snap_cells)
+
+    def plan_far(self, query, **opts):
+        """smp_plan_far: the staged plan for a goal across the room -- the free map of the folded-arm base lattice over
+        the query's environment, the route over it, the route checked densely and shortened, then plan() for the last
+        handover_distance metres.  opts: smp_far_opts' fields (pitch, n_theta, arm, handover_distance, map_margin,
+        window, snap_cells).  Returns plan()'s dict, its `path` led by the `far`["n_route_rows"] rows of the base stage;
+        `far` holds smp_far_info (stage, map, route, handover_node, n_route_rows, check, route_ms, total_ms).  Per-query
+        outcomes come back in `status`; failures of the call itself raise, as plan()'s do."""
+        o = L.FarOpts()
+        lib().smp_far_opts_default(ctypes.byref(o))
+        for k, v in opts.items():
+            if k == "arm":
+                for j in range(5):
+                    o.arm[j] = float(v[j])
+            else:
+                setattr(o, k, v)
+        r, info = L.Result(), L.FarInfo()
+        rc = lib().smp_plan_far(self.h, ctypes.byref(query), ctypes.byref(o), ctypes.byref(r), ctypes.byref(info))
+        d = _result_dict(r)
+        lib().smp_result_free(ctypes.byref(r))
+        if rc in _CALL_FAILURES:
+            raise L.SmpError(rc, "smp_plan_far")
+        d["far"] = dict(stage=info.stage, map=_fields(info.map), route=_route_info(info.route),
+                        handover_node=tuple(info.handover_node), n_route_rows=info.n_route_rows,
+                        check=_fields(info.check), route_ms=info.route_ms, total_ms=info.total_ms)
+        return d
+
     def clearance(self, q, max_dist=0.3, with_self=True, with_map=True):
         """smp_clearance_configs: distance of every configuration to the map (capped at max_dist) and to self-collision,
         one launch.  Returns a structured array (CLEARANCE_DTYPE: map, self, map_link, self_a, self_b; link indices
@@ -706,6 +753,68 @@ EDGE_CLEARANCE_DTYPE = np.dtype([("map", np.float64), ("self", np.float64), ("ma
 IK_DEVIATION = [(-0.005, 0.005)] * 3 + [(-0.025, 0.025)] * 3
 
 _CALL_FAILURES = (L.SMP_ERR_HIP, L.SMP_ERR_NO_DEVICE, L.SMP_ERR_PARSE)
+
+
+def _fields(s):
+    return {f: getattr(s, f) for f, _ in s._fields_}
+
+
+def _route_info(r):
+    return dict(from_node=tuple(r.from_node), to_node=tuple(r.to_node), n_chain=r.n_chain, n_settled=r.n_settled,
+                cost=r.cost)
+
+
+def _lattice(lattice):
+    """smp_base_lattice of an L.BaseLattice or of a dict of its fields."""
+    if isinstance(lattice, L.BaseLattice):
+        return lattice
+    lat = L.BaseLattice()
+    for k, v in (lattice._asdict() if hasattr(lattice, "_asdict") else dict(lattice)).items():
+        if k == "arm":
+            for j in range(5):
+                lat.arm[j] = float(v[j])
+        else:
+            setattr(lat, k, v)
+    return lat
+
+
+def base_lattice_fit(env_x, env_y, pitch, n_theta, theta0=0.0, arm=(-0.7, 1.9, 0.0, 1.7, 0.0)):
+    """smp_base_lattice_fit: the lattice over the environment env_x x env_y at `pitch` with n_theta headings of a full
+    circle from theta0 and the arm held at `arm` (default: pose_folded_arm).  Host only."""
+    ex, ey, a = (ctypes.c_double * 2)(*env_x), (ctypes.c_double * 2)(*env_y), (ctypes.c_double * 5)(*arm)
+    lat = L.BaseLattice()
+    check(lib().smp_base_lattice_fit(ex, ey, float(pitch), int(n_theta), float(theta0), a, ctypes.byref(lat)),
+          "smp_base_lattice_fit")
+    return lat
+
+
+def base_route(lattice, free, frm, to, snap_cells=2):
+    """smp_base_route: the cheapest route over the free nodes of `lattice` (free: base_free_map's (n_theta, ny, nx)
+    array) from the node of frm = (x, y, theta) to the node of to; blocked ends snap to a free node within snap_cells
+    rings.  Returns (rows (m, 8) with straight runs merged, chain (n_chain, 3) of (ix, iy, t), info dict).  Host only.
+    A failure raises SmpError with the dict as its `info` attribute."""
+    lat = _lattice(lattice)
+    f = np.asarray(free, bool).reshape(-1)
+    if len(f) != lat.nx * lat.ny * lat.n_theta:
+        raise ValueError("base_route: %d flags for a lattice of %d nodes" % (len(f), lat.nx * lat.ny * lat.n_theta))
+    packed = np.packbits(np.concatenate([f, np.zeros(-len(f) % 32, bool)]), bitorder="little")
+    bits = np.ascontiguousarray(packed).view(np.uint32) if len(packed) else np.zeros(1, np.uint32)
+    a, b = (ctypes.c_double * 3)(*frm), (ctypes.c_double * 3)(*to)
+    rows, n_out, chain, info = _pd(), ctypes.c_int64(), ctypes.POINTER(ctypes.c_int32)(), L.RouteInfo()
+    rc = lib().smp_base_route(ctypes.byref(lat), bits.ctypes.data_as(ctypes.c_void_p), a, b, int(snap_cells),
+                              ctypes.byref(rows), ctypes.byref(n_out), ctypes.byref(chain), ctypes.byref(info))
+    d = _route_info(info)
+    if rc != L.SMP_OK:
+        err = L.SmpError(rc, "smp_base_route")
+        err.info = d
+        raise err
+    try:
+        r = np.ctypeslib.as_array(rows, shape=(n_out.value, 8)).copy()
+        c = np.ctypeslib.as_array(chain, shape=(info.n_chain, 3)).copy()
+    finally:
+        lib().smp_buffer_free(rows)
+        lib().smp_buffer_free(chain)
+    return r, c, d
 
 
 def _margin(margin):
@@ -964,6 +1073,24 @@ class BiRRTstarPlanner:
         if r["status"] not in (L.SMP_OK, L.SMP_ERR_NO_SOLUTION):
             raise L.SmpError(r["status"], "run_planner")
         self._traj = [list(map(float, w)) for w in r["path"]]
+        return r["status"] == L.SMP_OK
+
+    def run_planner_far(self, flag_iter_or_time=1, max_iter_time=30.0, **opts):
+        """Not in the reference, where the branch is dead (squirrel_8dof_planner.cpp:505-508, 595-598): run_planner for
+        a goal across the room, the node's two-stage plan (GpuPlanner.plan_far) -- opts: arm (pose_folded_arm),
+        map_margin (astar_safety_distance), handover_distance (distance_birrt_star_planning), pitch, n_theta, window,
+        snap_cells.  `far_info` keeps the stages' record; the trajectory is the base stage's far_info["n_route_rows"]
+        rows followed by the 8-DoF plan's."""
+        if self._start is None:
+            return False
+        kw = dict(seconds=max_iter_time) if flag_iter_or_time else dict(iterations=int(max_iter_time))
+        q = GpuPlanner.make_query(self._start, self._goal, self._env[0], self._env[1], self._flags[0],
+                                  self._flags[1], seed=self.seed, query_id=self.query_id, **kw)
+        r = self._gpu.plan_far(q, **opts)
+        self.stats, self.far_info = r, r["far"]
+        if r["status"] not in (L.SMP_OK, L.SMP_ERR_NO_SOLUTION, L.SMP_ERR_START_INVALID, L.SMP_ERR_GOAL_INVALID):
+            raise L.SmpError(r["status"], "run_planner_far")
+        self._traj = [list(map(float, w)) for w in r["path"]] if r["status"] == L.SMP_OK else []
         return r["status"] == L.SMP_OK
 
     def getJointTrajectoryRef(self):
