@@ -157,6 +157,25 @@ class BiRRTstarPlanner {
   // Stages, counts and timing of the last run_planner_far.
   const smp_far_info& lastFar() const { return far_; }
 
+  // The cheapest cost from lattice node source = (ix, iy, t) to every node over a free map of smp_base_free_map
+  // (ceil(N / 32) words), on the device (smp_base_cost_field): cost gets N values, +inf for blocked and unreachable
+  // nodes; parent (may be NULL) N node numbers, -1 for the source and +inf nodes.  Throws on a failing call.
+  void base_cost_field(const smp_base_lattice& lattice, const std::vector<uint32_t>& free_bits, const int32_t source[3],
+                       std::vector<double>* cost, std::vector<int32_t>* parent = nullptr,
+                       smp_field_info* info = nullptr) {
+    if (!ready_ || !cost) throw std::runtime_error("smp: base_cost_field: no planner, or no output");
+    if (lattice.nx < 1 || lattice.ny < 1 || lattice.n_theta < 1)
+      throw std::runtime_error("smp: base_cost_field: an empty lattice");
+    const uint64_t n = (uint64_t)lattice.nx * (uint64_t)lattice.ny * (uint64_t)lattice.n_theta;
+    if (n > (uint64_t)SMP_LATTICE_MAX_NODES || free_bits.size() < (size_t)((n + 31) / 32))
+      throw std::runtime_error("smp: base_cost_field: the free map does not fit the lattice");
+    cost->assign((size_t)n, 0.0);
+    if (parent) parent->assign((size_t)n, -1);
+    const int st = smp_base_cost_field(planner_, &lattice, free_bits.data(), source, cost->data(),
+                                       parent ? parent->data() : nullptr, info);
+    if (st != SMP_OK) throw std::runtime_error(std::string("smp: smp_base_cost_field: ") + smp_strerror(st));
+  }
+
   void reset_planner_and_config() {
     reset_planner_only();
     env_x_[0] = env_x_[1] = env_y_[0] = env_y_[1] = 0.0;
@@ -833,7 +852,7 @@ class MultiGpuPlanner {
 inline bool planFar(birrt_star_motion_planning::BiRRTstarPlanner& planner, bool flag_iter_or_time, double max_iter_time,
                     const std::vector<double>& pose_folded_arm, double astar_safety_distance,
                     double distance_birrt_star_planning, smp_far_info* info = nullptr, double pitch = 0.0,
-                    int n_theta = 0) {
+                    int n_theta = 0, int route_device = 0) {
   if (pose_folded_arm.size() != 5) throw std::runtime_error("smp: planFar: pose_folded_arm has 5 joints");
   smp_far_opts o;
   smp_far_opts_default(&o);
@@ -842,6 +861,7 @@ inline bool planFar(birrt_star_motion_planning::BiRRTstarPlanner& planner, bool 
   o.handover_distance = distance_birrt_star_planning;
   if (pitch > 0.0) o.pitch = pitch;
   if (n_theta > 0) o.n_theta = n_theta;
+  o.route_device = route_device;  // 1: the route search on the device (smp_base_route_gpu), the same answer
   const bool ok = planner.run_planner_far(flag_iter_or_time, max_iter_time, o);
   if (info) *info = planner.lastFar();
   return ok;

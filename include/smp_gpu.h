@@ -661,10 +661,40 @@ typedef struct smp_route_info { int32_t from_node[3], to_node[3]; int64_t n_chai
 int smp_base_route(const smp_base_lattice* lat, const uint32_t* free_bits, const double from[3], const double to[3],
                    int snap_cells, double** out_rows, int64_t* n_out, int32_t** out_chain, smp_route_info* info);
 
+/* The cost field of a lattice: every node's cheapest cost from one source, on the device.
+ * smp_base_cost_field.  cost[n] (N doubles): the least left-to-right fp64 sum of step weights over routes source -> n in
+ *  smp_base_route's graph; +inf for a blocked or unreachable node.  parent[n] (N values): -1 for the source and for +inf
+ *  nodes, else the neighbour u with cost[u] + w == cost[n] and the least (cost[u], u).  Either output may be NULL.  Equal
+ *  bit for bit to smp_base_route's search run until its heap is empty: the field is the one solution of
+ *  cost[v] = min_u fl(cost[u] + w) while every weight still moves the largest finite cost; a field where the least
+ *  weight does not (fl(cost_max + w_min) == cost_max) is computed by the host search instead, fell_back = 1.
+ *  The free bits (ceil(N / 32) words) are uploaded; rounds of a tile-resident relaxation run as separate launches until
+ *  one changes nothing.  No scene is needed: the planner gives its device and stream.
+ *  SMP_ERR_ARG: a NULL planner, lattice, map or source, what smp_base_route refuses in a lattice, a source outside the
+ *  lattice or on a blocked node.  SMP_ERR_CAPACITY: N > SMP_LATTICE_MAX_NODES, or the device buffers cannot be had.
+ *  SMP_ERR_HIP: a failing runtime call, or more than n_free + 1 rounds.
+ * smp_base_route_gpu.  smp_base_route with the search on the device: the same snapping, statuses, chain, rows, cost and
+ *  n_settled (the nodes n with (cost[n], n) <= (cost[to], to); every reachable node where to is not reached).  Only the
+ *  chain, the cost and the counts are downloaded.  A NULL planner: SMP_ERR_ARG. */
+typedef struct smp_field_info {
+  int64_t n_nodes, n_reached;      /* reachable nodes, the source included */
+  int rounds, launches, fell_back; /* rounds up to and including the one that changed nothing; round launches enqueued */
+  int64_t tile_runs;               /* tile runs that did work */
+  double kernel_ms, total_ms;
+} smp_field_info;                  /* may be NULL */
+int smp_base_cost_field(smp_planner* p, const smp_base_lattice* lat, const uint32_t* free_bits,
+                        const int32_t source[3], double* cost, int32_t* parent, smp_field_info* info);
+int smp_base_route_gpu(smp_planner* p, const smp_base_lattice* lat, const uint32_t* free_bits, const double from[3],
+                       const double to[3], int snap_cells, double** out_rows, int64_t* n_out, int32_t** out_chain,
+                       smp_route_info* info, smp_field_info* finfo);
+/* The field's tile: FIELD_BX x FIELD_BY x FIELD_BT nodes into tile[3] (host only; what the tests size their maps by). */
+void smp_field_tile_shape(int tile[3]);
+
 /* smp_plan_far: the staged call.
  *  1. The lattice smp_base_lattice_fit(q->env_x, q->env_y, pitch, n_theta, 0, arm) and its free map at the margin
  *     {map_margin, 0}.  An unconfined query (env_x or env_y of (0, 0)): SMP_ERR_ARG.
- *  2. smp_base_route from q->start[0..2] to q->goal[0..2].
+ *  2. smp_base_route from q->start[0..2] to q->goal[0..2]; with route_device = 1 smp_base_route_gpu, whose answer is
+ *     the same (every output of the call but its times is).
  *  3. Handover: with the chain c_0 .. c_m, acc = 0 and j = m; while j > 0 and acc < handover_distance, the planar length
  *     of the step c_j -> c_j-1 (pitch, the diagonal weight, or 0 for a heading step) is added to acc and j decremented
  *     (squirrel_8dof_planner.cpp:1209-1215).  j == 0: no base stage, the call is smp_plan(p, q, out), n_route_rows = 0.
@@ -681,9 +711,10 @@ typedef struct smp_far_opts {
   double map_margin;          /* astar_safety_distance's role: margin of the free map and of the route's dense check; 0: boolean */
   int window;                 /* smp_shortcut_path's window over the route rows; <= 0: all pairs */
   int snap_cells;
+  int route_device;           /* 0: step 2 on the host (smp_base_route); 1: on the device (smp_base_route_gpu) */
 } smp_far_opts;
 void smp_far_opts_default(smp_far_opts*);
-    /* pitch 0.1, n_theta 8, arm = pose_folded_arm, handover 2.0, margin 0, window 0, snap 2 */
+    /* pitch 0.1, n_theta 8, arm = pose_folded_arm, handover 2.0, margin 0, window 0, snap 2, route on the host */
 typedef struct smp_far_info {
   int stage;                  /* where the call ended: 0 complete, 1 free map, 2 route search, 3 route check, 4 tail plan */
   smp_base_map_info map; smp_route_info route; int32_t handover_node[3];

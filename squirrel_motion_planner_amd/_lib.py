@@ -177,7 +177,13 @@ class RouteInfo(ctypes.Structure):
 class FarOpts(ctypes.Structure):
     """smp_far_opts: lattice, handover distance, map margin, shortcut window and snapping of smp_plan_far."""
     _fields_ = [("pitch", _d), ("n_theta", _i), ("arm", _d * 5), ("handover_distance", _d), ("map_margin", _d),
-                ("window", _i), ("snap_cells", _i)]
+                ("window", _i), ("snap_cells", _i), ("route_device", _i)]
+
+
+class FieldInfo(ctypes.Structure):
+    """smp_field_info: reached nodes, rounds, launches and timing of one cost-field solve on the device."""
+    _fields_ = [("n_nodes", _i64), ("n_reached", _i64), ("rounds", _i), ("launches", _i), ("fell_back", _i),
+                ("tile_runs", _i64), ("kernel_ms", _d), ("total_ms", _d)]
 
 
 class FarInfo(ctypes.Structure):
@@ -187,6 +193,7 @@ class FarInfo(ctypes.Structure):
 
 
 SMP_LATTICE_MAX_NODES = 1 << 26
+FIELD_TILE = (16, 16, 8)  # smp_field_tile_shape: the nodes (ix, iy, t) one tile of the cost field owns
 SMP_EDGE_MAX_POINTS = 1 << 20
 SMP_EDGE_TABLE_MAX = 1 << 20
 
@@ -268,6 +275,12 @@ EXPORTS = [
                                ctypes.POINTER(BaseMapInfo)]),
     ("smp_base_route", _i, [ctypes.POINTER(BaseLattice), _p, _pd, _pd, _i, ctypes.POINTER(_pd), ctypes.POINTER(_i64),
                             ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)), ctypes.POINTER(RouteInfo)]),
+    ("smp_base_cost_field", _i, [_p, ctypes.POINTER(BaseLattice), _p, ctypes.POINTER(ctypes.c_int32), _pd,
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(FieldInfo)]),
+    ("smp_base_route_gpu", _i, [_p, ctypes.POINTER(BaseLattice), _p, _pd, _pd, _i, ctypes.POINTER(_pd),
+                                ctypes.POINTER(_i64), ctypes.POINTER(ctypes.POINTER(ctypes.c_int32)),
+                                ctypes.POINTER(RouteInfo), ctypes.POINTER(FieldInfo)]),
+    ("smp_field_tile_shape", None, [ctypes.POINTER(ctypes.c_int)]),
     ("smp_far_opts_default", None, [ctypes.POINTER(FarOpts)]),
     ("smp_plan_far", _i, [_p, ctypes.POINTER(Query), ctypes.POINTER(FarOpts), ctypes.POINTER(Result),
                           ctypes.POINTER(FarInfo)]),

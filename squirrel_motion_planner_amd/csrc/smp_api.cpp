@@ -333,6 +333,7 @@ int smp_planner_create(int device, const smp_robot* robot, const smp_params* par
     need = std::max(need, margin_kernels_private_bytes());
     need = std::max(need, carve_kernels_private_bytes());
     need = std::max(need, lattice_kernels_private_bytes());
+    need = std::max(need, field_kernels_private_bytes());
     size_t cur = 0;
     if (hipDeviceGetLimit(&cur, hipLimitStackSize) == hipSuccess && cur < need) {
       need = (need + 255) / 256 * 256;
@@ -385,6 +386,8 @@ void smp_planner_destroy(smp_planner* p) {
   p->d_edges.release(); p->d_eorder.release(); p->d_efirst.release(); p->d_ecounter.release();
   p->d_gaps.release(); p->d_detours.release();
   p->d_clq.release(); p->d_clc.release(); p->d_cle.release(); p->d_mclear.release(); p->d_lbits.release();
+  p->d_fbits.release(); p->d_fcost.release(); p->d_factive.release(); p->d_fchanged.release(); p->d_fparent.release();
+  p->d_fchain.release(); p->d_fstats.release();
   p->d_bricks.release(); p->d_d2.release(); p->d_d2b.release(); p->d_slab.release();
   p->d_keys.release(); p->d_sbits.release(); p->d_sdil.release(); p->d_scount.release(); p->d_sk01.release();
   if (p->d_rb) (void)hipFree(p->d_rb);

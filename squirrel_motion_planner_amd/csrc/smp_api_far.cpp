@@ -1,5 +1,6 @@
 // C ABI implementation (include/smp_gpu.h "Far goals"): smp_plan_far, the staged call -- the base's free map
-// (smp_base_free_map, smp_api_paths.cpp), the route over it (smp_base_route, smp_route.cpp), the route's dense check
+// (smp_base_free_map, smp_api_paths.cpp), the route over it (smp_base_route, smp_route.cpp; with route_device
+// smp_base_route_gpu, smp_api_field.cpp, whose answer is the same), the route's dense check
 // (smp_shortcut_path_margin) and smp_plan for the tail.  It only composes entry points of the ABI: every stage is the
 // call a caller could make itself, so the stages' results are theirs bit for bit.
 #include <chrono>
@@ -45,6 +46,7 @@ extern "C" void smp_far_opts_default(smp_far_opts* o) {
   o->map_margin = 0.0;
   o->window = 0;
   o->snap_cells = 2;
+  o->route_device = 0;
 }
 
 extern "C" int smp_plan_far(smp_planner* p, const smp_query* q, const smp_far_opts* opts, smp_result* out,
@@ -82,7 +84,10 @@ extern "C" int smp_plan_far(smp_planner* p, const smp_query* q, const smp_far_op
   double* rows = nullptr;
   int64_t n_rows = 0;
   int32_t* chain = nullptr;
-  const int rs = smp_base_route(&lat, bits.data(), q->start, q->goal, o.snap_cells, &rows, &n_rows, &chain, &I.route);
+  const int rs = o.route_device
+                     ? smp_base_route_gpu(p, &lat, bits.data(), q->start, q->goal, o.snap_cells, &rows, &n_rows, &chain,
+                                          &I.route, nullptr)
+                     : smp_base_route(&lat, bits.data(), q->start, q->goal, o.snap_cells, &rows, &n_rows, &chain, &I.route);
   I.route_ms = ms_since(t_route);
   std::free(rows);  // (the rows wanted are those of the chain up to the handover)
   if (rs != SMP_OK) return leave(2, rs);

@@ -12,6 +12,7 @@
 #include "../../include/smp_gpu.h"
 #include "smp_carve.h"
 #include "smp_clearance.h"
+#include "smp_field.h"
 #include "smp_pass.h"
 #include "smp_host.h"
 #include "smp_ik.h"
@@ -130,6 +131,13 @@ struct smp_planner {
   smp::DBuf<uint8_t> d_mclear;
   // the base's free map (smp_base_free_map): one word per tile of 32 lattice nodes; the work counter is d_ecounter
   smp::DBuf<uint32_t> d_lbits;
+  // the cost field (smp_base_cost_field / smp_base_route_gpu): the uploaded free bits, the costs, the tiles' activity
+  // flags of both round parities, a batch's per-round changed counters, parents, the walked chain, the small record
+  smp::DBuf<uint32_t> d_fbits;
+  smp::DBuf<double> d_fcost;
+  smp::DBuf<unsigned> d_factive, d_fchanged;
+  smp::DBuf<int32_t> d_fparent, d_fchain;
+  smp::DBuf<smp::FieldStats> d_fstats;
   // self filter (smp_planner_set_carve / smp_carve_keys): the sticky carve of the device scene builds, its links by
   // name (resolved against the robot at every build), and the carve launches' scratch: the world items, the flags of
   // the standalone call, the carved-key count; ev2 / ev3 time the carve launches inside a build

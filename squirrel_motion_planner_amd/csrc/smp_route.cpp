@@ -66,16 +66,6 @@ int64_t handover_index(const LatticeDev& lat, const int32_t* chain, int64_t n, d
 
 namespace {
 
-struct Lattice {
-  LatticeDev d;
-  int nx, ny, nt, wrap;
-  const uint32_t* bits;
-  int64_t node(int ix, int iy, int t) const { return ((int64_t)t * ny + iy) * nx + ix; }
-  bool free_at(int ix, int iy, int t) const {
-    return ix >= 0 && ix < nx && iy >= 0 && iy < ny && lattice_free(bits, node(ix, iy, t));
-  }
-};
-
 // floor(v + 0.5) as an index, false where it is not finite or does not fit an int.
 bool round_index(double v, int64_t* out) {
   const double f = std::floor(v + 0.5);
@@ -86,7 +76,7 @@ bool round_index(double v, int64_t* out) {
 
 // The node (x, y, theta) snaps to: SMP_ERR_ARG outside the lattice, `blocked` where no free node is found within
 // snap_cells rings of the same heading layer.
-int snap(const Lattice& L, const double p[3], int snap_cells, int blocked, int32_t node[3]) {
+int snap(const RouteLattice& L, const double p[3], int snap_cells, int blocked, int32_t node[3]) {
   if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return SMP_ERR_ARG;
   int64_t ix, iy, t;
   if (!round_index((p[0] - L.d.x0) / L.d.pitch, &ix) || !round_index((p[1] - L.d.y0) / L.d.pitch, &iy) ||
@@ -121,6 +111,105 @@ int snap(const Lattice& L, const double p[3], int snap_cells, int blocked, int32
 }
 
 }  // namespace
+
+RouteWeights route_weights(const LatticeDev& d) {
+  return RouteWeights{d.pitch, std::sqrt(d.pitch * d.pitch + d.pitch * d.pitch), std::fabs(d.dtheta)};
+}
+
+int route_lattice(const smp_base_lattice* lat, const uint32_t* free_bits, RouteLattice* L) {
+  if (int st = lattice_dev(lat, &L->d)) return st;
+  L->nx = lat->nx;
+  L->ny = lat->ny;
+  L->nt = lat->n_theta;
+  L->wrap = lat->wrap_theta ? 1 : 0;
+  L->bits = free_bits;
+  return SMP_OK;
+}
+
+int route_ends(const RouteLattice& L, const double from[3], const double to[3], int snap_cells, smp_route_info* r) {
+  int st = snap(L, from, snap_cells, SMP_ERR_START_INVALID, r->from_node);
+  if (st != SMP_OK) {
+    for (int k = 0; k < 3; ++k) r->from_node[k] = -1;
+    return st;
+  }
+  st = snap(L, to, snap_cells, SMP_ERR_GOAL_INVALID, r->to_node);
+  if (st != SMP_OK)
+    for (int k = 0; k < 3; ++k) r->to_node[k] = -1;
+  return st;
+}
+
+bool route_search(const RouteLattice& L, int64_t src, int64_t dst, std::vector<double>* dp_out,
+                  std::vector<int32_t>* parent_out, int64_t* n_settled) {
+  *n_settled = 0;
+  const int64_t N = L.d.n, layer = (int64_t)L.nx * L.ny;
+  const RouteWeights w = route_weights(L.d);
+  const double w_axis = w.axis, w_diag = w.diag, w_turn = w.turn;
+  std::vector<double>& dp = *dp_out;
+  std::vector<int32_t>& parent = *parent_out;
+  dp.assign((size_t)N, std::numeric_limits<double>::infinity());
+  parent.assign((size_t)N, -1);
+  std::vector<bool> settled((size_t)N, false);
+  typedef std::pair<double, int64_t> Item;
+  std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
+  dp[(size_t)src] = 0.0;
+  heap.push(Item(0.0, src));
+  static const int AX[4][2] = {{0, -1}, {-1, 0}, {1, 0}, {0, 1}};
+  static const int DG[4][2] = {{-1, -1}, {1, -1}, {-1, 1}, {1, 1}};
+  bool found = false;
+  while (!heap.empty()) {
+    const int64_t u = heap.top().second;
+    heap.pop();
+    if (settled[(size_t)u]) continue;
+    settled[(size_t)u] = true;
+    ++*n_settled;
+    if (u == dst) {
+      found = true;
+      break;
+    }
+    const int t = (int)(u / layer), iy = (int)((u - (int64_t)t * layer) / L.nx), ix = (int)(u % L.nx);
+    const double du = dp[(size_t)u];
+    auto relax = [&](int64_t v, double w) {
+      const double c = du + w;
+      if (c < dp[(size_t)v]) {
+        dp[(size_t)v] = c;
+        parent[(size_t)v] = (int32_t)u;
+        heap.push(Item(c, v));
+      }
+    };
+    for (const auto& a : AX)
+      if (L.free_at(ix + a[0], iy + a[1], t)) relax(L.node(ix + a[0], iy + a[1], t), w_axis);
+    for (const auto& g : DG)
+      if (L.free_at(ix + g[0], iy + g[1], t) && L.free_at(ix + g[0], iy, t) && L.free_at(ix, iy + g[1], t))
+        relax(L.node(ix + g[0], iy + g[1], t), w_diag);
+    for (int s = -1; s <= 1; s += 2) {
+      int tt = t + s;
+      if (L.wrap) tt = (tt + L.nt) % L.nt;
+      if (tt >= 0 && tt < L.nt && L.free_at(ix, iy, tt)) relax(L.node(ix, iy, tt), w_turn);
+    }
+  }
+  return found;
+}
+
+int route_output(const RouteLattice& L, const std::vector<int32_t>& chain, double** out_rows, int64_t* n_out,
+                 int32_t** out_chain) {
+  const std::vector<double> rows = chain_rows(L.d, chain.data(), (int64_t)(chain.size() / 3));
+  double* rbuf = (double*)std::malloc(rows.size() * sizeof(double));
+  int32_t* cbuf = out_chain ? (int32_t*)std::malloc(chain.size() * sizeof(int32_t)) : nullptr;
+  if (!rbuf || (out_chain && !cbuf)) {
+    std::free(rbuf);
+    std::free(cbuf);
+    return SMP_ERR_CAPACITY;
+  }
+  std::memcpy(rbuf, rows.data(), rows.size() * sizeof(double));
+  *out_rows = rbuf;
+  *n_out = (int64_t)(rows.size() / NJ);
+  if (out_chain) {
+    std::memcpy(cbuf, chain.data(), chain.size() * sizeof(int32_t));
+    *out_chain = cbuf;
+  }
+  return SMP_OK;
+}
+
 }  // namespace smp
 
 using namespace smp;
@@ -163,71 +252,18 @@ extern "C" int smp_base_route(const smp_base_lattice* lat, const uint32_t* free_
   for (int k = 0; k < 3; ++k) r.from_node[k] = r.to_node[k] = -1;
   if (info) *info = r;
   if (!lat || !free_bits || !from || !to || !out_rows || !n_out) return SMP_ERR_ARG;
-  Lattice L;
-  if (int st = lattice_dev(lat, &L.d)) return st;
-  L.nx = lat->nx;
-  L.ny = lat->ny;
-  L.nt = lat->n_theta;
-  L.wrap = lat->wrap_theta ? 1 : 0;
-  L.bits = free_bits;
-  int st = snap(L, from, snap_cells, SMP_ERR_START_INVALID, r.from_node);
-  if (st != SMP_OK) {
-    for (int k = 0; k < 3; ++k) r.from_node[k] = -1;
-  } else {
-    st = snap(L, to, snap_cells, SMP_ERR_GOAL_INVALID, r.to_node);
-    if (st != SMP_OK)
-      for (int k = 0; k < 3; ++k) r.to_node[k] = -1;
-  }
-  if (st != SMP_OK) {
+  RouteLattice L;
+  if (int st = route_lattice(lat, free_bits, &L)) return st;
+  if (int st = route_ends(L, from, to, snap_cells, &r)) {
     if (info) *info = r;
     return st;
   }
-  const int64_t N = L.d.n, layer = (int64_t)L.nx * L.ny;
+  const int64_t layer = (int64_t)L.nx * L.ny;
   const int64_t src = L.node(r.from_node[0], r.from_node[1], r.from_node[2]);
   const int64_t dst = L.node(r.to_node[0], r.to_node[1], r.to_node[2]);
-  const double w_axis = L.d.pitch, w_diag = std::sqrt(L.d.pitch * L.d.pitch + L.d.pitch * L.d.pitch);
-  const double w_turn = std::fabs(L.d.dtheta);
-  std::vector<double> dp((size_t)N, std::numeric_limits<double>::infinity());
-  std::vector<int32_t> parent((size_t)N, -1);
-  std::vector<bool> settled((size_t)N, false);
-  typedef std::pair<double, int64_t> Item;
-  std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
-  dp[(size_t)src] = 0.0;
-  heap.push(Item(0.0, src));
-  static const int AX[4][2] = {{0, -1}, {-1, 0}, {1, 0}, {0, 1}};
-  static const int DG[4][2] = {{-1, -1}, {1, -1}, {-1, 1}, {1, 1}};
-  bool found = false;
-  while (!heap.empty()) {
-    const int64_t u = heap.top().second;
-    heap.pop();
-    if (settled[(size_t)u]) continue;
-    settled[(size_t)u] = true;
-    ++r.n_settled;
-    if (u == dst) {
-      found = true;
-      break;
-    }
-    const int t = (int)(u / layer), iy = (int)((u - (int64_t)t * layer) / L.nx), ix = (int)(u % L.nx);
-    const double du = dp[(size_t)u];
-    auto relax = [&](int64_t v, double w) {
-      const double c = du + w;
-      if (c < dp[(size_t)v]) {
-        dp[(size_t)v] = c;
-        parent[(size_t)v] = (int32_t)u;
-        heap.push(Item(c, v));
-      }
-    };
-    for (const auto& a : AX)
-      if (L.free_at(ix + a[0], iy + a[1], t)) relax(L.node(ix + a[0], iy + a[1], t), w_axis);
-    for (const auto& g : DG)
-      if (L.free_at(ix + g[0], iy + g[1], t) && L.free_at(ix + g[0], iy, t) && L.free_at(ix, iy + g[1], t))
-        relax(L.node(ix + g[0], iy + g[1], t), w_diag);
-    for (int s = -1; s <= 1; s += 2) {
-      int tt = t + s;
-      if (L.wrap) tt = (tt + L.nt) % L.nt;
-      if (tt >= 0 && tt < L.nt && L.free_at(ix, iy, tt)) relax(L.node(ix, iy, tt), w_turn);
-    }
-  }
+  std::vector<double> dp;
+  std::vector<int32_t> parent;
+  const bool found = route_search(L, src, dst, &dp, &parent, &r.n_settled);
   if (!found) {
     if (info) *info = r;
     return SMP_ERR_NO_SOLUTION;
@@ -244,22 +280,7 @@ extern "C" int smp_base_route(const smp_base_lattice* lat, const uint32_t* free_
   // (collected goal first as t, iy, ix: reversed it is start first, ix, iy, t)
   for (size_t a = 0, b = chain.size() - 1; a < b; ++a, --b) std::swap(chain[a], chain[b]);
   r.n_chain = (int64_t)(chain.size() / 3);
-  const std::vector<double> rows = chain_rows(L.d, chain.data(), r.n_chain);
-  double* rbuf = (double*)std::malloc(rows.size() * sizeof(double));
-  int32_t* cbuf = out_chain ? (int32_t*)std::malloc(chain.size() * sizeof(int32_t)) : nullptr;
-  if (!rbuf || (out_chain && !cbuf)) {
-    std::free(rbuf);
-    std::free(cbuf);
-    if (info) *info = r;
-    return SMP_ERR_CAPACITY;
-  }
-  std::memcpy(rbuf, rows.data(), rows.size() * sizeof(double));
-  *out_rows = rbuf;
-  *n_out = (int64_t)(rows.size() / NJ);
-  if (out_chain) {
-    std::memcpy(cbuf, chain.data(), chain.size() * sizeof(int32_t));
-    *out_chain = cbuf;
-  }
+  const int os = route_output(L, chain, out_rows, n_out, out_chain);
   if (info) *info = r;
-  return SMP_OK;
+  return os;
 }

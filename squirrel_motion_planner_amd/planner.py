@@ -481,13 +481,47 @@ class GpuPlanner:
         """smp_base_route over a free map of base_free_map: the module's base_route (host only)."""
         return base_route(lattice, free, frm, to, snap_cells)
 
+    def base_cost_field(self, lattice, free, source, want_parent=True):
+        """smp_base_cost_field: the cheapest cost from node source = (ix, iy, t) to every node of `lattice` over the
+        free map `free` (base_free_map's array), computed on the device.  Returns (cost (n_theta, ny, nx) float64, +inf
+        where blocked or unreachable; parent (n_theta, ny, nx) int32 node numbers, -1 for the source and +inf nodes, or
+        None with want_parent=False; info dict of smp_field_info)."""
+        lat = _lattice(lattice)
+        bits = _packed_free("base_cost_field", lat, free)
+        n = lat.nx * lat.ny * lat.n_theta
+        cost = np.empty(n, np.float64)
+        parent = np.empty(n, np.int32) if want_parent else None
+        info = L.FieldInfo()
+        src = (ctypes.c_int32 * 3)(*[int(v) for v in source])
+        check(lib().smp_base_cost_field(self.h, ctypes.byref(lat), bits.ctypes.data_as(ctypes.c_void_p), src,
+                                        cost.ctypes.data_as(_pd),
+                                        parent.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if want_parent else None,
+                                        ctypes.byref(info)), "smp_base_cost_field")
+        shape = (lat.n_theta, lat.ny, lat.nx)
+        return cost.reshape(shape), parent.reshape(shape) if want_parent else None, _fields(info)
+
+    def base_route_gpu(self, lattice, free, frm, to, snap_cells=2):
+        """smp_base_route_gpu: base_route with the search on the device.  Returns (rows, chain, info dict, field info
+        dict); a failure raises SmpError with the two dicts as its `info` and `field` attributes."""
+        lat = _lattice(lattice)
+        bits = _packed_free("base_route_gpu", lat, free)
+        finfo = L.FieldInfo()
+        try:
+            call = lambda *a: lib().smp_base_route_gpu(self.h, *a, ctypes.byref(finfo))
+            r, c, d = _route_call("smp_base_route_gpu", call, lat, bits, frm, to, snap_cells)
+        except L.SmpError as err:
+            err.field = _fields(finfo)
+            raise
+        return r, c, d, _fields(finfo)
+
     def plan_far(self, query, **opts):
         """smp_plan_far: the staged plan for a goal across the room -- the free map of the folded-arm base lattice over
         the query's environment, the route over it, the route checked densely and shortened, then plan() for the last
         handover_distance metres.  opts: smp_far_opts' fields (pitch, n_theta, arm, handover_distance, map_margin,
-        window, snap_cells).  Returns plan()'s dict, its `path` led by the `far`["n_route_rows"] rows of the base stage;
-        `far` holds smp_far_info (stage, map, route, handover_node, n_route_rows, check, route_ms, total_ms).  Per-query
-        outcomes come back in `status`; failures of the call itself raise, as plan()'s do."""
+        window, snap_cells, route_device -- 1: the route search on the device, the same answer).  Returns plan()'s
+        dict, its `path` led by the `far`["n_route_rows"] rows of the base stage; `far` holds smp_far_info (stage, map,
+        route, handover_node, n_route_rows, check, route_ms, total_ms).  Per-query outcomes come back in `status`;
+        failures of the call itself raise, as plan()'s do."""
         o = L.FarOpts()
         lib().smp_far_opts_default(ctypes.byref(o))
         for k, v in opts.items():
@@ -794,18 +828,28 @@ def base_route(lattice, free, frm, to, snap_cells=2):
     rings.  Returns (rows (m, 8) with straight runs merged, chain (n_chain, 3) of (ix, iy, t), info dict).  Host only.
     A failure raises SmpError with the dict as its `info` attribute."""
     lat = _lattice(lattice)
+    return _route_call("smp_base_route", lib().smp_base_route, lat, _packed_free("base_route", lat, free), frm, to,
+                       snap_cells)
+
+
+def _packed_free(what, lat, free):
+    """The words of a free map (n_theta, ny, nx) of `lat`: bit n % 32 of word n / 32."""
     f = np.asarray(free, bool).reshape(-1)
     if len(f) != lat.nx * lat.ny * lat.n_theta:
-        raise ValueError("base_route: %d flags for a lattice of %d nodes" % (len(f), lat.nx * lat.ny * lat.n_theta))
+        raise ValueError("%s: %d flags for a lattice of %d nodes" % (what, len(f), lat.nx * lat.ny * lat.n_theta))
     packed = np.packbits(np.concatenate([f, np.zeros(-len(f) % 32, bool)]), bitorder="little")
-    bits = np.ascontiguousarray(packed).view(np.uint32) if len(packed) else np.zeros(1, np.uint32)
+    return np.ascontiguousarray(packed).view(np.uint32) if len(packed) else np.zeros(1, np.uint32)
+
+
+def _route_call(name, fn, lat, bits, frm, to, snap_cells):
+    """One route call (smp_base_route's arguments from the lattice on): (rows, chain, info dict)."""
     a, b = (ctypes.c_double * 3)(*frm), (ctypes.c_double * 3)(*to)
     rows, n_out, chain, info = _pd(), ctypes.c_int64(), ctypes.POINTER(ctypes.c_int32)(), L.RouteInfo()
-    rc = lib().smp_base_route(ctypes.byref(lat), bits.ctypes.data_as(ctypes.c_void_p), a, b, int(snap_cells),
-                              ctypes.byref(rows), ctypes.byref(n_out), ctypes.byref(chain), ctypes.byref(info))
+    rc = fn(ctypes.byref(lat), bits.ctypes.data_as(ctypes.c_void_p), a, b, int(snap_cells),
+            ctypes.byref(rows), ctypes.byref(n_out), ctypes.byref(chain), ctypes.byref(info))
     d = _route_info(info)
     if rc != L.SMP_OK:
-        err = L.SmpError(rc, "smp_base_route")
+        err = L.SmpError(rc, name)
         err.info = d
         raise err
     try:
@@ -1079,8 +1123,8 @@ class BiRRTstarPlanner:
         """Not in the reference, where the branch is dead (squirrel_8dof_planner.cpp:505-508, 595-598): run_planner for
         a goal across the room, the node's two-stage plan (GpuPlanner.plan_far) -- opts: arm (pose_folded_arm),
         map_margin (astar_safety_distance), handover_distance (distance_birrt_star_planning), pitch, n_theta, window,
-        snap_cells.  `far_info` keeps the stages' record; the trajectory is the base stage's far_info["n_route_rows"]
-        rows followed by the 8-DoF plan's."""
+        snap_cells, route_device.  `far_info` keeps the stages' record; the trajectory is the base stage's
+        far_info["n_route_rows"] rows followed by the 8-DoF plan's."""
         if self._start is None:
             return False
         kw = dict(seconds=max_iter_time) if flag_iter_or_time else dict(iterations=int(max_iter_time))
