@@ -10,7 +10,7 @@
 
 using namespace smp;
 
-// The last query's state in the oracle's terms (test infrastructure, DESIGN.md "Large trees": the oracle continues
+// The state of the last call's query 0 in the oracle's terms (test infrastructure, DESIGN.md "Large trees": the oracle continues
 // the same run from it, orc_resume_*): per tree the child lists (first child, next sibling: the GPU inserts children
 // at the head, so the reference's out-edge order is the list reversed) and every node's in-edge (interpolation start
 // and target, n x 8 row-major); then the loop scalars (iv: iteration, checked, valid, first_iter, last_iter,

@@ -738,8 +738,10 @@ class GpuPlanner:
         return par, conf, cost
 
     def export_state(self):
-        """The last query's state in the form oracle.Oracle.resume() takes (test infrastructure: the oracle continues
-        the GPU's run from it -- large-tree parity and the CPU timed at the GPU's tree sizes)."""
+        """The state of query 0 of the last plan / plan_batch call (the library keeps that query's buffers and tree
+        sizes; after a batch it is the batch's first query, not its last) in the form oracle.Oracle.resume() takes.
+        Test infrastructure: the oracle continues the GPU's run from it -- large-tree parity and the CPU timed at the
+        GPU's tree sizes -- and tests/tree_audit.py audits it, after single-query calls."""
         iv = np.zeros(16, np.int64)
         dv = np.zeros(25)
         check(lib().smp_probe_export_state(self.h, iv.ctypes.data_as(ctypes.c_void_p), dv.ctypes.data_as(_pd)),

@@ -158,14 +158,20 @@ def test_oracle_invalid_start_goal(orobot):
 
 
 def test_oracle_tree_invariants(orobot):
-    """no_two_parents_check / cost consistency (birrt_star.cpp:6812-6860) on a seeded run."""
+    """no_two_parents_check / cost consistency (birrt_star.cpp:6812-6860) on a seeded run: the tree audit
+    (tree_audit.py: one parent and one child entry per node, every cost from its parent's and the configurations, the
+    connection record, the path and the cost rows) reports nothing."""
+    import tree_audit
     sc = scenes.box_room()
     orc = O.Oracle(orobot, O.OracleScene(sc.keys, sc.res))
     r = orc.plan(sc.start, sc.goal, env_x=sc.env_x, env_y=sc.env_y, max_iter=250, seed=11)
+    rep = tree_audit.audit(orc.export_state(r), tree_audit.from_oracle(r), sc.start, sc.goal,
+                           O.DEFAULT_PARAMS["n_pts"], O.DEFAULT_PARAMS["near_r"], np.array(orobot.rev, bool))
+    assert rep.ok and rep.skipped == [], str(rep)
+    assert {"A1.reach[start]", "A1.children_once[goal]", "A3.edge_cost[start]", "A3.edge_cost[goal]"} <= set(rep.residuals)
     for t in ("start", "goal"):
         par = r[t + "_parent"]
         assert par[0] == 0
-        assert np.all(par[1:] < np.arange(1, len(par)) + 10**9)
         # every node reaches the root (no loops)
         for i in range(len(par)):
             j, steps = i, 0
